@@ -13,10 +13,16 @@ no collective on the decode path); aggregate tokens/s = N*
 Weights and context are synthetic (no checkpoints / datasets offline): random bf16 weights in the named
 shapes, context state from shadowkv_amd.llama.build_synthetic_context, per-layer query random walk.
 
-Prints ONE JSON line on rank 0 (metric / roofline / cpu_baseline: see DESIGN.md "Measurement").  Besides the headline
-the line carries (N = 1 only): the chunk hit rate of the TIMED steps, the pinned hit rates 0 % and 60 % (SURVEY.md 8d;
-the reference's own test assumes 154/256, kernels/test_cached_gather_copy.cu:61), the reference slot order
-(`--layout reference`), and short lines for BASELINE.json configs 2 and 3.
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up, warms up, times exactly --steps
+steps and prints the headline (`value`, `ms_per_step`, the chunk hit rate of the TIMED steps, `per_rank`).  `--full`
+adds everything else, each leg a run of its own (N = 1 only unless noted): roofline of the scan kernel (any N),
+cpu_baseline, the pinned hit rates 0 % and 60 % (the reference's own test assumes 154/256,
+kernels/test_cached_gather_copy.cu:61), the reference slot order (`--layout reference`), the call-order / eager
+variants, short lines for BASELINE.json configs 2 and 3 and the reference's other regimes, batched runs, the
+full-attention pair, the prefill-side builders.
+`--dump-outputs DIR`: after the timed steps, the last timed step's results (`tokens.npy`: the sampled token of every
+sequence, float64; `logits.npy`: its logits, float32) are written to DIR; inputs are seeded, so equal arguments give
+equal inputs from run to run.
 """
 import argparse
 import json
@@ -151,14 +157,55 @@ def pinned_eviction(model, pin):
     return lambda: view.copy_(filler)
 
 
-def run_decode(model, args, ctx, steps, warmup, walk_step, seed, world=1, pin_hit=None):
+MAX_DUMP_BYTES = 64 << 20      # --dump-outputs: all arrays together
+
+
+def record_logits(model, holder):
+    """Wraps the model's two forward entry points (forward_fused: the fused step, eager or captured; inference: the call
+    order) so holder["logits"] is the tensor the latest step's forward returned - under a captured graph the graph's own
+    output buffer, which every replay rewrites.  Returns the function that removes the wrappers."""
+    names = ("forward_fused", "inference")
+    for name in names:
+        def rec(*a, _fn=getattr(model, name), **k):
+            out = _fn(*a, **k)
+            holder["logits"] = out
+            return out
+        setattr(model, name, rec)
+    return lambda: [model.__dict__.pop(n, None) for n in names]
+
+
+def dump_outputs(outputs, out_dir, limit=MAX_DUMP_BYTES):
+    """Writes every CPU tensor of `outputs` as out_dir/<name>.npy: floating point as float32, integers as float64 (exact up
+    to 2^53).  If the arrays exceed `limit` bytes together, each is cut to a fixed sample of its elements (same positions from
+    run to run: seeded, in ascending order), written flat with the flat positions beside it as <name>_index.npy."""
+    import numpy as np
+    arrs = {n: (t.double() if not t.is_floating_point() else t.float()).numpy() for n, t in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        if total > limit:
+            # a share of the limit in proportion to the array's size; a kept element costs its value + an f64 index
+            # (16 B per array held back: an array cut to its one-element minimum stays inside the limit)
+            share = (limit - 16 * len(arrs)) * a.nbytes // total
+            keep = max(1, share // (a.itemsize + 8))
+            idx = torch.randperm(a.size, generator=torch.Generator().manual_seed(0))[:keep].sort().values.numpy()
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(arrs)
+
+
+def run_decode(model, args, ctx, steps, warmup, walk_step, seed, world=1, pin_hit=None, outputs=None):
     """warmup + exactly `steps` timed decode steps (barrier + synchronize on both sides, MAX over ranks).
-    Returns dict(value, ms_per_step, hit_rate (of the timed steps), mode, slack_ring)."""
+    Returns dict(value, ms_per_step, hit_rate (of the timed steps), mode, slack_ring).  outputs: a dict that receives, as CPU
+    tensors, what the last timed step computed: `tokens` [bs] (the sampled tokens) and `logits` [bs, vocab] f32."""
     from shadowkv_amd import llama
     cache, cfg = model.kv_cache, model.cfg
     full = model.attn_mode == "full"
     bs = model.batch_size
     dev = model.device
+    last = {}
+    unwrap = record_logits(model, last) if outputs is not None else None
     rewind(model, ctx)
     slack = (cache.k_cache.shape[-2] - ctx) if full else (cache.k_cache_buffer.shape[-2] - cache.sparse_end)
     slack_ring = warmup + steps + 3 > slack
@@ -222,6 +269,10 @@ def run_decode(model, args, ctx, steps, warmup, walk_step, seed, world=1, pin_hi
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
+    if outputs is not None:
+        unwrap()
+        outputs["tokens"] = next_token[:, -1].cpu()
+        outputs["logits"] = last["logits"][:, -1, :].float().cpu()
     h1 = int(dec.hit_accum) if dec is not None else float(hits_eager)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -651,13 +702,16 @@ def measure_fetch_launch(model, ctx, walk_step, steps=3, seed=31):
                     steps, "" if early is None else " (early fetch off for this measurement: all miss bytes cross the link inside the launch)"))
 
 
-def run_call_order(model, ctx, steps, warmup, walk_step, seed, lazy_v=True, inplace=False, reference_calls=False):
+def run_call_order(model, ctx, steps, warmup, walk_step, seed, lazy_v=True, inplace=False, reference_calls=False,
+                   outputs=None):
     """The drop-in path: DecoderLM.decode_step(fused=False) = the reference's call order (inference -> layer_compute:
     pre_attention_compute, apply_rotary_pos_emb, update_kv_cache, get_retrieval_position_ids, get_value_cache under
     copy_stream || get_key_cache, attention, post_attention_compute; models/base.py:315-341, models/llama.py:354-427),
-    the reference's slot order, eager launches, per-step host read of the token."""
+    the reference's slot order, eager launches, per-step host read of the token.  outputs: as run_decode's."""
     from shadowkv_amd import llama
     cache = model.kv_cache
+    last = {}
+    unwrap = record_logits(model, last) if outputs is not None else None
     rewind(model, ctx)
     walk = llama.QueryWalk(model, step=walk_step, seed=seed)
     model.query_hook = walk
@@ -683,7 +737,12 @@ def run_call_order(model, ctx, steps, warmup, walk_step, seed, lazy_v=True, inpl
             step()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if outputs is not None:
+            outputs["tokens"] = tok[:, -1].cpu()
+            outputs["logits"] = last["logits"][:, -1, :].float().cpu()
     finally:
+        if unwrap is not None:
+            unwrap()
         model.query_hook = None
         cache.lazy_value_fetch, cache.inplace_methods = lazy_before, inplace_before
         cache.reference_calls = False
@@ -944,13 +1003,18 @@ def main(argv=None):
                          "the ~50 ranges that can hold a top-k logit (same token); 0: the sampler streams the whole logit row")
     ap.add_argument("--overlap-splits", type=int, default=0,
                     help="tuning: split-attention workgroups per head inside the fetch launch (0: the default, 24)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline line only (no sweep / secondary workloads)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short lines for BASELINE.json configs 2 and 3")
-    ap.add_argument("--no-batched", action="store_true", help="skip the bs 8 / bs 24 lines (the reference's published regime)")
-    ap.add_argument("--no-pair", action="store_true", help="skip the e2e-style full-attention / ShadowKV pair")
-    ap.add_argument("--batched", default="8,24", help="batch sizes of the `batched` entries of the default run")
-    ap.add_argument("--no-batched-resident", action="store_true", help="skip the 512-resident-slot run of every `batched` entry")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement (roofline, CPU baseline, sweeps, variants, "
+                         "secondary workloads, batched runs, the full-attention pair); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: roofline and CPU baseline only (no sweep / secondary workloads)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the short lines for BASELINE.json configs 2 and 3")
+    ap.add_argument("--no-batched", action="store_true", help="--full: skip the bs 8 / bs 24 lines (the reference's published regime)")
+    ap.add_argument("--no-pair", action="store_true", help="--full: skip the e2e-style full-attention / ShadowKV pair")
+    ap.add_argument("--batched", default="8,24", help="batch sizes of the `batched` entries of the --full run")
+    ap.add_argument("--no-batched-resident", action="store_true", help="--full: skip the 512-resident-slot run of every `batched` entry")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -970,6 +1034,7 @@ def main(argv=None):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     bind_to_launcher_cpulist()
     dev, numa = setup_device(local_rank)
+    torch.manual_seed(1234 + rank)      # the first token and the eager sampler's draws: equal arguments, equal inputs
     if world > 1:
         import torch.distributed as dist
         if DIST_BACKEND == "nccl":
@@ -981,17 +1046,20 @@ def main(argv=None):
     bs = args.batch
     model, cfg, ctx, budget, t_build = build_model(args.workload, args, rank, dev)
     cache = model.kv_cache
+    dump = {"outputs": {}} if args.dump_outputs else {}
     if args.mode == "call_order":
         if world > 1 or full or bs != 1:
             print("--mode call_order: one GPU, one sequence, ShadowKV attention", file=sys.stderr)
             sys.exit(2)
         r = run_call_order(model, ctx, args.steps, args.warmup, args.walk_step, seed=99 + rank, lazy_v=not args.strict_call_order,
-                           inplace=args.inplace_methods)
+                           inplace=args.inplace_methods, **dump)
         head = dict(value=r["value"], ms_per_step=r["ms_per_step"], hit_rate=r["chunk_hit_rate"], mode="call_order",
                     slack_ring=False, elapsed_local=r["ms_per_step"] * 1e-3 * args.steps, steps=args.steps)
     else:
         head = run_decode(model, args, ctx, args.steps, args.warmup, args.walk_step, seed=99 + rank, world=world,
-                          pin_hit=args.pin_hit_rate)
+                          pin_hit=args.pin_hit_rate, **dump)
+    if dump and rank == 0:
+        dump_outputs(dump["outputs"], args.dump_outputs)
 
     # one diagnostic record per rank, gathered to rank 0 (no effect on the timed region above)
     my_rec = rank_record(rank, local_rank, model, head, t_build, numa)
@@ -1003,8 +1071,9 @@ def main(argv=None):
         out = None
         try:
             extras = {}
-            detail = world == 1 and not args.no_extras and not full
-            roof = measure_score_kernel(model) if not full else None
+            # a plain run stops at the headline; every leg below is a run of its own and belongs to --full
+            detail = args.full and world == 1 and not args.no_extras and not full
+            roof = measure_score_kernel(model) if args.full and not full else None
             if detail:
                 path_ms, path_hit = measure_path_only(model, args.walk_step)
                 wbytes = model.weight_bytes()
@@ -1172,7 +1241,7 @@ def main(argv=None):
                 # context only (other hardware, the reference's own batch regime): never a vs_baseline
                 out["reference_published_same_batch"] = {"value": 245.90, "unit": "tokens/s", "hardware": "1x A100", "batch": 24,
                                                          "source": "index.html:210-214 (config test/e2e.py:63-68)"}
-            if world == 1 and bs == 1 and not full and not args.no_cpu_baseline:
+            if args.full and world == 1 and bs == 1 and not full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(model, args.walk_step)
             if detail and not args.no_secondary and args.workload == "llama31_122k" and bs == 1 and args.layers is None:
                 import gc

@@ -114,7 +114,7 @@ def _stub_bench(bench, rank):
         calls["build"] += 1
         return model, cfg, 124928, 2048, 1.5 + rank_
 
-    def run_decode(model_, args, ctx, steps, warmup, walk_step, seed, world=1, pin_hit=None):
+    def run_decode(model_, args, ctx, steps, warmup, walk_step, seed, world=1, pin_hit=None, outputs=None):
         # the timed region's collectives exactly as bench.run_decode issues them (barrier, barrier, MAX of the elapsed time)
         calls["decode"] += 1
         dist.barrier()
@@ -122,6 +122,9 @@ def _stub_bench(bench, rank):
         dist.barrier()
         t = torch.tensor([elapsed_local], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        if outputs is not None:                          # what the last timed step computed (as bench.run_decode fills it)
+            outputs["tokens"] = torch.tensor([7 + rank])
+            outputs["logits"] = torch.arange(cfg.vocab_size, dtype=torch.float32).view(1, -1) + rank
         return dict(value=bench.aggregate_throughput([steps] * world, [float(t)]), ms_per_step=float(t) / steps * 1e3,
                     hit_rate=0.6 + 0.1 * rank, mode=args.mode, slack_ring=False, elapsed_local=elapsed_local, steps=steps)
 
@@ -137,7 +140,7 @@ def _stub_bench(bench, rank):
     return calls
 
 
-def _worker_main(rank, world, port, out):
+def _worker_main(rank, world, port, out, extra=()):
     import contextlib
     import io
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), LOCAL_RANK=str(rank),
@@ -146,7 +149,7 @@ def _worker_main(rank, world, port, out):
     calls = _stub_bench(bench, rank)
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "10", "--warmup", "2"])
+        bench.main(["--gpus", str(world), "--steps", "10", "--warmup", "2", *extra])
     # main() has destroyed the process group behind its final barrier: every rank got here
     out[rank] = (buf.getvalue(), dict(calls), dist.is_initialized())
 
@@ -156,7 +159,7 @@ def test_bench_main_on_two_ranks_prints_one_line_on_rank_zero():
     port = _free_port()
     with mp.Manager() as mgr:
         out = mgr.dict()
-        mp.spawn(_worker_main, args=(2, port, out), nprocs=2, join=True)
+        mp.spawn(_worker_main, args=(2, port, out, ("--full",)), nprocs=2, join=True)
         out = dict(out)
     (text0, calls0, init0), (text1, calls1, init1) = out[0], out[1]
     assert text1 == "" and calls1 == dict(build=1, decode=1, score=0)       # rank 1: decodes, prints and measures nothing else
@@ -173,6 +176,74 @@ def test_bench_main_on_two_ranks_prints_one_line_on_rank_zero():
     assert "replicas x2" in rec["config"]["parallelism"] and rec["roofline"]["frac"] == 0.5
     for key in ("cpu_baseline", "secondary", "batched", "hit_rate_sweep"):  # N = 1 extras are not run at N > 1
         assert key not in rec
+
+
+def test_plain_bench_main_times_the_headline_only_and_dumps_rank_zero_outputs(tmp_path):
+    """Without --full, main() builds, times and prints the headline and nothing else: no roofline launch, no extra legs.
+    --dump-outputs writes rank 0's last-step arrays (integers as float64, floating point as float32)."""
+    import json
+    import numpy as np
+    port = _free_port()
+    with mp.Manager() as mgr:
+        out = mgr.dict()
+        mp.spawn(_worker_main, args=(2, port, out, ("--dump-outputs", str(tmp_path / "dump"))), nprocs=2, join=True)
+        out = dict(out)
+    (text0, calls0, _), (text1, calls1, _) = out[0], out[1]
+    assert calls0 == calls1 == dict(build=1, decode=1, score=0) and text1 == ""
+    lines = [l for l in text0.splitlines() if l.strip()]
+    assert len(lines) == 1, text0
+    rec = json.loads(lines[0])
+    assert rec["value"] == 2 * 10 / 1.0 and rec["ms_per_step"] == 100.0 and rec["steps"] == 10 and rec["warmup"] == 2
+    assert rec["higher_is_better"] is True and rec["dtype"] == "bf16" and rec["unit"] == "tokens/s"
+    assert [r["rank"] for r in rec["per_rank"]] == [0, 1]
+    for key in ("roofline", "cpu_baseline", "secondary", "batched", "hit_rate_sweep", "bench_error"):
+        assert key not in rec
+    assert sorted(os.listdir(tmp_path / "dump")) == ["logits.npy", "tokens.npy"]
+    tok, lg = np.load(tmp_path / "dump" / "tokens.npy"), np.load(tmp_path / "dump" / "logits.npy")
+    assert tok.dtype == np.float64 and tok.tolist() == [7.0]                  # rank 0's
+    assert lg.dtype == np.float32 and lg.shape == (1, 128) and lg[0, 5] == 5.0
+
+
+def test_dump_outputs_types_and_size_cap(tmp_path):
+    """bench.dump_outputs: float32 / float64 files; over the size limit every array becomes the same seeded sample of its
+    elements (with the flat positions beside it), so two runs still compare element for element."""
+    import bench
+    import numpy as np
+    outs = dict(tokens=torch.tensor([3, 128255]), logits=torch.randn(4, 1000, dtype=torch.bfloat16))
+    assert bench.dump_outputs(outs, str(tmp_path / "a")) == ["logits", "tokens"]
+    tok = np.load(tmp_path / "a" / "tokens.npy")
+    assert tok.dtype == np.float64 and tok.tolist() == [3.0, 128255.0]
+    lg = np.load(tmp_path / "a" / "logits.npy")
+    assert lg.dtype == np.float32 and np.array_equal(lg, outs["logits"].float().numpy())
+    for d in ("b", "c"):
+        bench.dump_outputs(outs, str(tmp_path / d), limit=4000)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["logits.npy", "logits_index.npy", "tokens.npy", "tokens_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in files) <= 4000     # (128 B: the .npy header)
+    idx = np.load(tmp_path / "b" / "logits_index.npy").astype(np.int64)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "logits_index.npy")) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "logits.npy"), outs["logits"].float().numpy().reshape(-1)[idx])
+
+
+def test_record_logits_keeps_the_latest_forward_output():
+    """bench.record_logits: the wrapped forward entry points hand their result through unchanged and leave the latest one
+    in the holder; the returned function restores the class's own methods."""
+    import types
+    import bench
+
+    class M:
+        def forward_fused(self, x):
+            return x + 1
+
+        def inference(self, x):
+            return x * 2
+    m, holder = M(), {}
+    undo = bench.record_logits(m, holder)
+    assert m.forward_fused(1) == 2 and holder["logits"] == 2
+    assert m.inference(5) == 10 and holder["logits"] == 10
+    undo()
+    assert "forward_fused" not in vars(m) and "inference" not in vars(m)
+    assert isinstance(m.forward_fused, types.MethodType) and m.forward_fused(1) == 2
 
 
 def _plain_bench(extra_env=None, args=("--gpus", "2", "--steps", "10", "--warmup", "2")):
@@ -211,7 +282,7 @@ def test_a_failing_reporting_leg_still_leaves_the_line():
     """Everything behind the timed headline runs guarded: a leg that raises is reported in the line (`bench_error`), the headline
     value is still printed and the exit code stays 0."""
     import json
-    r = _plain_bench({"SKV_TEST_BREAK_SCORE": "1"})
+    r = _plain_bench({"SKV_TEST_BREAK_SCORE": "1"}, args=("--gpus", "2", "--steps", "10", "--warmup", "2", "--full"))
     assert r.returncode == 0, r.stderr
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout

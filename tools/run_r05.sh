@@ -7,8 +7,9 @@ if [ "$what" = tests ]; then
   echo "rc=$rc" >> gpurun_out/${tag}_tests.txt; tail -5 gpurun_out/${tag}_tests.txt
   exit $rc
 fi
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || { tail -20 gpurun_out/${tag}_bench.err; exit 1; }
-python tools/show_bench.py gpurun_out/${tag}_bench.json 2>/dev/null | cut -c1-400
+res=bench_results; mkdir -p $res      # the full bench line (roofline, CPU baseline, secondary workloads, ...) and its log
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $res/${tag}_bench.json 2> $res/${tag}_bench.err || { tail -20 $res/${tag}_bench.err; exit 1; }
+python tools/show_bench.py $res/${tag}_bench.json 2>/dev/null | cut -c1-400
 tools/prof.sh ${tag} --steps 24 --warmup 6 | cut -c1-170 || exit 1
 tools/prof.sh ${tag}_glm --workload glm4_200k --steps 16 --warmup 6 | cut -c1-170 || exit 1
 tools/pmc_score.sh ${tag} | tail -24
