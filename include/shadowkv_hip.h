@@ -538,6 +538,24 @@ SKV_EXPORT int skv_host_free(void* p);
 SKV_EXPORT int skv_chunk_stats(const void* k, long long block_stride, int blocks, int chunks, int chunk_size,
                     int head_dim, void* means, void* min_cos, skv_stream_t stream);
 
+/* ---- part 5: prefill attention ----------------------------------------------------------------------------------------- */
+
+/* Causal GQA flash attention over a prompt (flash_attn_with_kvcache(q, k, v, causal=True) at
+ * models/base.py:293 and :311 of the reference): out[b][i][h] = softmax_j(scale q[b][h][i] . k[b][h / G][j]) v[b][h / G][j]
+ * over the keys j <= kv_len - q_len + i (the mask aligned bottom-right: kv_len == q_len is a prompt, kv_len > q_len a
+ * continuation on a cache).  G = q_heads / kv_heads, any value.  bf16 in / out, f32 accumulation, the softmax weights rounded
+ * to bf16 for the P.V product.
+ * q [bs][q_heads][q_len][head_dim], k / v [bs][kv_heads][kv_len][head_dim] given as (batch, head, row) strides in elements with
+ * the last dimension contiguous; every stride a multiple of 8 and every pointer 16-byte aligned.
+ * out [bs][q_len][q_heads][head_dim] contiguous (flash-attn's output layout).
+ * SKV_ERR_ARG: a null pointer, q_len < 1, kv_len < q_len, q_heads % kv_heads != 0, a misaligned stride or pointer;
+ * SKV_ERR_UNSUPPORTED: head_dim != 128. */
+SKV_EXPORT int skv_prefill_attention(const void* q, const void* k, const void* v, void* out, int batch_size, int q_heads,
+                          int kv_heads, int q_len, int kv_len, int head_dim, long long q_stride_b, long long q_stride_h,
+                          long long q_stride_s, long long k_stride_b, long long k_stride_h, long long k_stride_s,
+                          long long v_stride_b, long long v_stride_h, long long v_stride_s, float scale,
+                          skv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

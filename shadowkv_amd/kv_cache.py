@@ -1010,6 +1010,14 @@ class ShadowKVCache_CPU:
         """Rows left for generated tokens behind the sparse region (buf_len - sparse_end; 96 at the 122K config)."""
         return self.k_cache_buffer.shape[-2] - self.sparse_end - self.gen_offset
 
+    def generated_row_slack_after_prefill(self, incoming):
+        """generated_row_slack() as it will be right after prefill_kv_cache of an `incoming`-token prompt (the same row
+        arithmetic), so that a caller can refuse a generation length before any layer runs."""
+        chunks = incoming // self.chunk_size - self.local_chunk
+        chunks -= chunks % 8
+        sparse_end = incoming - chunks * self.chunk_size + self.outlier_chunk * self.chunk_size + self.resident_budget
+        return self.k_cache_buffer.shape[-2] - sparse_end
+
     def incoming_rows_writable(self, incoming):
         """True when `incoming` new rows fit behind the sparse region (a caller that pushes them itself must not write past
         the buffer; the reference drops such rows)."""

@@ -279,8 +279,10 @@ class DecoderLM:
     # --------------------------------------------------------------- decode branch of layer_compute (base.py:315-341)
     @torch.inference_mode()
     def layer_compute(self, layer, layer_idx, hidden_states, position_ids):
-        residual = hidden_states
         bsz, q_len, _ = hidden_states.shape
+        if q_len > 1 and (self.attn_mode == "full" or q_len > self.PREFILL_MIN_LEN):
+            return self._prefill_layer(layer, layer_idx, hidden_states, position_ids)
+        residual = hidden_states
         q, k, v = self.pre_attention_compute(hidden_states, layer)
         q, k = self.apply_rotary_pos_emb(q, k, position_ids, layer_idx=layer_idx)
         if self.query_hook is not None and not self._hook_applied:
@@ -306,6 +308,136 @@ class DecoderLM:
         attn = tensor_op.sparse_attention_decode(q, k_view, v_view, out=None if sc is None or q_len != 1 or sc["bs"] != bsz
                                                  else sc["sets"][sc["i"]]["attn"])
         return self.post_attention_compute(attn.reshape(bsz, q_len, self.hidden_size), residual, layer)
+
+    # --------------------------------------------------------------- prefill branch of layer_compute (base.py:281-313)
+    PREFILL_MIN_LEN = 4 * 1024        # base.py:299: a ShadowKV layer takes its prefill branch above this many tokens
+
+    def _prefill_layer(self, layer, layer_idx, hidden_states, position_ids):
+        """One layer over a token sequence.  ShadowKV cache (base.py:299-313): get_svd on the pre-RoPE keys -> RoPE ->
+        prefill_kv_cache(v, l, k_roped, q[:, :, -1:]) -> causal attention over the prompt.  Full-attention cache
+        (base.py:281-296): RoPE -> update_kv_cache -> causal attention over the cached rows plus the new ones.  Then the dense
+        tail, in sequence slices once bsz * q_len > 64 K tokens (base.py:351-364)."""
+        residual = hidden_states
+        bsz, q_len, _ = hidden_states.shape
+        q, k, v = self.pre_attention_compute(hidden_states, layer)
+        cache = self.kv_cache
+        if self.attn_mode == "full":
+            q, k = self.apply_rotary_pos_emb(q, k, position_ids)
+            k_all, v_all = cache.update_kv_cache(k, v, layer_idx)
+            attn = tensor_op.causal_attention_prefill(q, k_all, v_all)
+        else:
+            cache.get_svd(k, layer_idx=layer_idx)
+            q, k = self.apply_rotary_pos_emb(q, k, position_ids)
+            cache.prefill_kv_cache(v, layer_idx, k, q[:, :, -1:])
+            attn = tensor_op.causal_attention_prefill(q, k, v)
+        del q, k, v
+        attn = attn.reshape(bsz, q_len, self.hidden_size)
+        if bsz * q_len <= 64 * 1024:
+            return self.post_attention_compute(attn, residual, layer)
+        out = torch.empty_like(attn)
+        step = bsz * q_len // (bsz * q_len // (8 * 1024))
+        for s0 in range(0, q_len, step):
+            out[:, s0:s0 + step] = self.post_attention_compute(attn[:, s0:s0 + step], residual[:, s0:s0 + step], layer)
+        return out
+
+    def _prefill_forward(self, input_ids):
+        """Every layer over input_ids [b, n] at positions kv_len .. kv_len + n - 1 (the cache's own sub-batch bookkeeping
+        places the rows), then the final norm and lm_head on the last position only (base.py:150-155): [b, 1, V] f32."""
+        hs = F.embedding(input_ids, self.embed_tokens)
+        pos = self.get_ctx(input_ids)
+        for idx in range(self.num_layers):
+            hs = self._prefill_layer(self.layers[idx], idx, hs, pos)
+        hs = tensor_op.layer_norm(hs[:, -1:, :], self.norm_variance_epsilon, self.norm_weight)
+        return F.linear(hs, self.lm_head).float()
+
+    def _check_prompt(self, n, gen_len=0):
+        """ValueError, before any layer runs, for a prompt of n tokens (then gen_len decode steps) the model cannot serve."""
+        if n < 1 or n > self.max_length:
+            raise ValueError(f"prompt of {n} tokens: it must hold 1 .. max_length = {self.max_length} tokens")
+        c = self.kv_cache
+        if self.attn_mode != "full":
+            if n <= self.PREFILL_MIN_LEN or n <= c.sparse_budget:
+                raise ValueError(f"a ShadowKV prompt must be longer than {self.PREFILL_MIN_LEN} tokens and than the sparse "
+                                 f"budget ({c.sparse_budget}); got {n}")
+            slack = c.generated_row_slack_after_prefill(n)
+            if gen_len > slack:
+                raise ValueError(f"gen_len {gen_len} exceeds the {slack} cache rows left for generated tokens after a "
+                                 f"{n}-token prompt")
+        elif n + gen_len > c.k_cache.shape[-2]:
+            raise ValueError(f"{n} prompt + {gen_len} generated tokens exceed the {c.k_cache.shape[-2]} cache rows")
+        if n + gen_len > self.cos_sin_cache.shape[0]:
+            raise ValueError(f"{n} prompt + {gen_len} generated tokens run past the RoPE table ({self.cos_sin_cache.shape[0]} "
+                             "rows = max_length + max_new_tokens)")
+
+    @torch.inference_mode()
+    def prefill(self, input_ids):
+        """base.py:163-186: clear the cache, run every layer over the prompt [batch_size, n]; returns the last position's
+        logits [batch_size, 1, V] f32."""
+        n = input_ids.size(1)
+        self._check_prompt(n)
+        self.kv_cache.clear()
+        logits = self._prefill_forward(input_ids)
+        assert self.kv_cache.get_kv_len() == n, f"KV length mismatch, got {self.kv_cache.get_kv_len()}, expected {n}"
+        return logits
+
+    @torch.inference_mode()
+    def prefill_cont(self, input_ids):
+        """base.py:188-206 on the full-attention cache: the chunk's rows go behind the cached ones and attend all of them
+        (the causal mask aligned bottom-right)."""
+        if self.attn_mode != "full":
+            raise NotImplementedError("prefill_cont needs attn_mode='full': on a ShadowKV cache the reference sends such a chunk "
+                                      "down its decode branch (base.py:299), which this model serves one token at a time")
+        past, n = self.kv_cache.get_kv_len(), input_ids.size(1)
+        if past + n > self.max_length:
+            raise ValueError(f"{past} cached + {n} new tokens exceed max_length = {self.max_length}")
+        logits = self._prefill_forward(input_ids)
+        assert self.kv_cache.get_kv_len() == past + n
+        return logits
+
+    @torch.inference_mode()
+    def batch_prefill(self, input_ids, sub_batch=None):
+        """base.py:500-548: the batch in sub-batches of 8 sequences for prompts between 120 K and 200 K tokens, of 4 otherwise
+        (sub_batch overrides), each through the cache's sub-batched prefill.  Returns [batch_size, 1, V] f32."""
+        bs, n = input_ids.shape
+        if bs != self.batch_size:
+            raise ValueError(f"batch size {bs} != the model's {self.batch_size}")
+        self._check_prompt(n)
+        T = int(sub_batch) if sub_batch else (8 if 120 * 1024 < n < 200 * 1024 else 4)
+        self.kv_cache.clear()
+        logits = torch.zeros(bs, 1, self.vocab_size, device=self.device, dtype=torch.float32)
+        for b0 in range(0, bs, T):
+            logits[b0:b0 + T].copy_(self._prefill_forward(input_ids[b0:b0 + T]))
+        assert self.kv_cache.get_kv_len() == n, f"KV length mismatch, got {self.kv_cache.get_kv_len()}, expected {n}"
+        return logits
+
+    @torch.inference_mode()
+    def generate(self, input_ids, gen_len, temperature=0.0, top_p=0.9, top_k=50, eos_token_id=None, graph=False):
+        """base.py:386-470 without a tokenizer: batch_prefill -> sample -> H2D -> gen_len decode steps (the fused step, or a
+        captured GraphDecoder replayed with graph=True).  Returns the generated ids [batch_size, 1 + gen_len] (int64),
+        fewer when every sequence has produced eos_token_id."""
+        n = input_ids.size(1)
+        self._check_prompt(n, int(gen_len))
+        logits = self.batch_prefill(input_ids)
+        tok = tensor_op.sample_token(logits[:, -1, :], temperature=temperature, top_p=top_p, top_k=top_k,
+                                     state=self._sampler_state)
+        self.kv_cache.H2D()
+        out = [tok.clone()]
+
+        def done():
+            return eos_token_id is not None and bool((out[-1] == eos_token_id).all())
+
+        if graph and gen_len > 0 and not done():
+            dec = GraphDecoder(self, temperature=temperature, top_p=top_p, top_k=top_k)
+            dec.token.copy_(tok)
+            dec.capture(warmup=1)                   # the warm-up step is an eager step: its token is in dec.token
+            out.append(dec.token.clone())
+            while len(out) <= gen_len and not done():
+                out.append(dec.step().clone())
+        else:
+            while len(out) <= gen_len and not done():
+                tok = self.decode_step(tok, temperature=temperature, top_p=top_p, top_k=top_k)
+                out.append(tok.clone())
+        return torch.cat(out, dim=1)
 
     # --------------------------------------------------------------- fused decode step (MI355X launch sequence)
     @torch.inference_mode()

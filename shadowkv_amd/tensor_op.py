@@ -7,6 +7,7 @@ Names, argument order and return values follow the reference so `models/llama.py
   apply_rotary_pos_emb_cuda_push_cache, batch_gather_gemm_rotary_pos_emb_cuda, sample_token, ...
 plus what replaces third-party CUDA packages on this path:
   sparse_attention_decode  (flash_attn_with_kvcache at base.py:341, q_len == 1)
+  causal_attention_prefill (flash_attn_with_kvcache(causal=True) at base.py:293 / :311, the prompt)
   silu_and_mul, rotary_embedding_neox  (vllm._custom_ops at llama.py:296,421)
 `minference_prefill_kernel` (MInference sparse prefill) is outside the decode path and raises.
 """
@@ -311,6 +312,41 @@ def sparse_attention_decode(q, k_cache, v_cache, kv_len=None, kv_len_dev=None, s
     check(lib().skv_sparse_attention(ptr(q), ptr(k_cache), ptr(v_cache), ptr(out), ptr(ws), ptr(kv_len_dev),
                                      int(kv_len), rows, k_cache.stride(1), bs, Hq, Hkv, D, splits, 1.0 / math.sqrt(D),
                                      current_stream_handle()), "sparse_attention")
+    return out
+
+
+def causal_attention_prefill(q, k, v, out=None):
+    """Causal GQA attention over a prompt: flash_attn_with_kvcache(q, k, v, causal=True) at base.py:293 / :311, one native
+    launch (skv_prefill_attention).  q [bs, Hq, S, D]; k / v [bs, Hkv, kv_len, D] views with kv_len >= S (any batch / head /
+    row strides, last dimension contiguous: the transpose view of the fused QKV output, slices of the cache buffers).  Row i
+    attends keys j <= kv_len - S + i (the mask aligned bottom-right).  Returns [bs, S, Hq, D] (flash-attn's layout: a
+    reshape to [bs, S, Hq * D] is free).  bf16, D = 128."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q must be [bs, Hq, S, D], k / v [bs, Hkv, kv_len, D]")
+    bs, Hq, S, D = q.shape
+    Hkv, kv_len = k.shape[1], k.shape[2]
+    if k.shape != v.shape or k.shape[0] != bs or k.shape[3] != D:
+        raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"{Hq} query heads are not a multiple of {Hkv} KV heads")
+    if S < 1 or kv_len < S:
+        raise ValueError(f"kv_len {kv_len} must be >= q_len {S} >= 1")
+    if not (q.dtype == k.dtype == v.dtype == torch.bfloat16) or not (q.is_cuda and k.is_cuda and v.is_cuda):
+        raise ValueError("q / k / v must be bf16 tensors on the GPU")
+
+    def strides(t):             # (a size-1 dimension's stride is never followed: 0 keeps it out of the alignment check)
+        return [st if n > 1 else 0 for n, st in zip(t.shape[:3], t.stride()[:3])]
+
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.stride(3) != 1 or any(st % 8 for st in strides(t)) or t.data_ptr() % 16:
+            raise ValueError(f"{name} must have a contiguous last dimension, strides that are multiples of 8 elements and a "
+                             "16-byte aligned start")
+    if out is None:
+        out = torch.empty(bs, S, Hq, D, dtype=q.dtype, device=q.device)
+    elif out.shape != (bs, S, Hq, D) or not out.is_contiguous() or out.dtype != q.dtype:
+        raise ValueError("out must be a contiguous [bs, S, Hq, D] tensor of q's dtype")
+    check(lib().skv_prefill_attention(ptr(q), ptr(k), ptr(v), ptr(out), bs, Hq, Hkv, S, kv_len, D, *strides(q), *strides(k),
+                                      *strides(v), 1.0 / math.sqrt(D), current_stream_handle()), "prefill_attention")
     return out
 
 
