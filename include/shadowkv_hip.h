@@ -556,6 +556,39 @@ SKV_EXPORT int skv_prefill_attention(const void* q, const void* k, const void* v
                           long long v_stride_b, long long v_stride_h, long long v_stride_s, float scale,
                           skv_stream_t stream);
 
+/* ---- part 6: MInference vertical + slash sparse prefill --------------------------------------------------------------- */
+
+/* The reference's minference_prefill_kernel (models/tensor_op.py:68-117), kv_len == q_len == L; contract in DESIGN.md
+ * section 9.  q [bs][q_heads][L][head_dim], k / v [bs][kv_heads][L][head_dim] given as (batch, head, row) strides in elements
+ * with the last dimension contiguous, every stride a multiple of 8 and q / k / v / out 16-byte aligned; G = q_heads / kv_heads.
+ * Both entries only launch (no allocation, no synchronisation): graph-capturable.  Every argument check runs on the host
+ * before any launch.  SKV_ERR_ARG: a null pointer, a size < 1, kv_len != q_len, q_heads % kv_heads != 0, a misaligned stride
+ * or pointer; SKV_ERR_UNSUPPORTED: head_dim != 128. */
+
+/* Bytes of the workspace skv_vs_estimate / skv_vs_sparse_attention need (0 for a size < 1). */
+SKV_EXPORT long long skv_vs_estimate_workspace_bytes(int batch_size, int q_heads, int q_len);
+SKV_EXPORT long long skv_vs_attention_workspace_bytes(int batch_size, int q_heads, int q_len);
+
+/* Index estimate from the last m = min(64, L) queries r: A[r][j] = q_r . k_j (no 1 / sqrt(D) scale), -inf for j > r,
+ * P = softmax_j(A) in f32.  col_score[b][h][j] = sum_r P[r][j], +inf for j < 30; diag_score[b][h][s] = sum_r P[r][r - s],
+ * +inf for s < 100 (s in [0, L)).  Both f32 [bs][q_heads][L] contiguous; deterministic (no atomics). */
+SKV_EXPORT int skv_vs_estimate(const void* q, const void* k, void* col_score, void* diag_score, void* workspace,
+                    int batch_size, int q_heads, int kv_heads, int q_len, int kv_len, int head_dim, long long q_stride_b,
+                    long long q_stride_h, long long q_stride_s, long long k_stride_b, long long k_stride_h,
+                    long long k_stride_s, skv_stream_t stream);
+
+/* Sparse causal attention: query row i (block b = i / 64, e = 64 (b + 1)) attends key j <= i iff j is in the vertical set or
+ * in a window [max(e - s, 64) - 64, max(e - s, 64)) of a slash offset s < e; softmax(scale q . k) over those keys times v,
+ * f32 accumulation, the weights rounded to bf16 for P.V.  vertical_idx int32 [bs][q_heads][n_vertical] and slash_idx int32
+ * [bs][q_heads][n_slash], each row sorted ascending; duplicates allowed, entries outside [0, L) ignored (pad with INT_MAX).
+ * out [bs][L][q_heads][head_dim] contiguous.  A row that attends no key writes zeros. */
+SKV_EXPORT int skv_vs_sparse_attention(const void* q, const void* k, const void* v, void* out, const void* vertical_idx,
+                            const void* slash_idx, void* workspace, int batch_size, int q_heads, int kv_heads, int q_len,
+                            int kv_len, int head_dim, int n_vertical, int n_slash, long long q_stride_b,
+                            long long q_stride_h, long long q_stride_s, long long k_stride_b, long long k_stride_h,
+                            long long k_stride_s, long long v_stride_b, long long v_stride_h, long long v_stride_s,
+                            float scale, skv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,10 @@ _SIGS = {
     "skv_sparse_attention": (c_int, [c_p] * 6 + [c_int, c_int, c_ll] + [c_int] * 5 + [c_f, c_p]),
     "skv_sparse_attention_slots": (c_int, [c_p] * 6 + [c_int, c_int, c_ll] + [c_int] * 5 + [c_f, c_p] + [c_int] * 3 + [c_p]),
     "skv_prefill_attention": (c_int, [c_p] * 4 + [c_int] * 6 + [c_ll] * 9 + [c_f, c_p]),
+    "skv_vs_estimate_workspace_bytes": (c_ll, [c_int] * 3),
+    "skv_vs_attention_workspace_bytes": (c_ll, [c_int] * 3),
+    "skv_vs_estimate": (c_int, [c_p] * 5 + [c_int] * 6 + [c_ll] * 6 + [c_p]),
+    "skv_vs_sparse_attention": (c_int, [c_p] * 7 + [c_int] * 8 + [c_ll] * 9 + [c_f, c_p]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -12,7 +12,9 @@ Weights: there are no checkpoints offline, so layers are created with random bf1
 named architecture's shapes (`random_init=True`); `load_state(...)` accepts real tensors with the same
 fused layouts (wqkv = [q;k;v], gate_up = [gate;up]) as llama.py:111-128.
 """
+import json
 import math
+import os
 from dataclasses import dataclass
 
 import torch
@@ -80,11 +82,36 @@ def build_cos_sin_cache(cfg, max_pos, device, dtype):
     return torch.cat((freqs.cos(), freqs.sin()), dim=-1).to(dtype).contiguous()
 
 
+MINFERENCE_DEFAULT = ("vertical_and_slash", 1000, 6096, 1)   # MInference's entry for a head its config does not list
+
+
+def load_minference_pattern(pattern, num_layers, num_heads):
+    """The per-layer MInference patterns: None (every head MINFERENCE_DEFAULT), a path to a JSON file in the reference's
+    format (a list with one {"head": [type, vertical_size, slash_size, score]} object per layer) or such a list.  Returns a
+    list of num_layers dicts {int head: (type, v, s, score)} covering every head (missing heads get MINFERENCE_DEFAULT);
+    ValueError for a wrong layer count, a head outside [0, num_heads), an unknown type, "block_sparse" or a size that is not
+    a positive integer."""
+    if pattern is None:
+        pattern = [{} for _ in range(num_layers)]
+    elif isinstance(pattern, (str, os.PathLike)):
+        with open(pattern) as f:
+            pattern = json.load(f)
+    if not isinstance(pattern, (list, tuple)):
+        raise ValueError("minference_pattern must be None, a JSON path or a list with one dict per layer")
+    if len(pattern) != num_layers:
+        raise ValueError(f"minference_pattern has {len(pattern)} layers, the model {num_layers}")
+    out = []
+    for i, layer in enumerate(pattern):
+        d = tensor_op.validate_minference_layer(layer, num_heads, where=f"minference_pattern layer {i}")
+        out.append({h: d.get(h, MINFERENCE_DEFAULT) for h in range(num_heads)})
+    return out
+
+
 class DecoderLM:
     def __init__(self, cfg=LLAMA_3_1_8B, batch_size=1, max_length=64 * 1024, device="cuda:0", dtype=torch.bfloat16,
                  attn_mode="shadowkv_cpu", sparse_budget=2048, rank=160, chunk_size=8, random_init=True, seed=1234,
                  num_layers=None, chunk_layout="reference", v_offload=True, overlap_attention=False, max_new_tokens=1024,
-                 resident_sets=None):
+                 resident_sets=None, minference=False, minference_pattern=None):
         if chunk_layout not in ("reference", "inplace"):
             raise ValueError("chunk_layout must be 'reference' (hits compacted to the front, the reference's slot order) "
                              "or 'inplace' (hits keep their slots, misses take the freed slots)")
@@ -103,6 +130,11 @@ class DecoderLM:
         self.head_dim = cfg.hidden_size // cfg.num_attention_heads
         self.num_layers = num_layers or cfg.num_hidden_layers
         self.vocab_size = cfg.vocab_size
+        # MInference sparse prefill (base.py:289-291 / :308-310): one {head: (type, v, s, score)} dict per
+        # layer, the reference's attribute name; validated before anything is allocated so that a bad pattern never fails partway through a prefill
+        self.minference = bool(minference)
+        self.minference_parttern = (load_minference_pattern(minference_pattern, self.num_layers, self.num_heads)
+                                    if self.minference else None)
         gen = torch.Generator(device=self.device).manual_seed(seed)
         if not random_init:
             raise NotImplementedError("no checkpoints are available offline; use random_init=True or load_state()")
@@ -324,12 +356,19 @@ class DecoderLM:
         if self.attn_mode == "full":
             q, k = self.apply_rotary_pos_emb(q, k, position_ids)
             k_all, v_all = cache.update_kv_cache(k, v, layer_idx)
-            attn = tensor_op.causal_attention_prefill(q, k_all, v_all)
+            if self.minference and k_all.shape[2] == q_len:
+                # (a prefill_cont chunk on top of cached rows keeps the dense kernel: the estimate assumes kv_len == q_len)
+                attn = tensor_op.minference_prefill_kernel(q, k_all, v_all, self.minference_parttern[layer_idx])
+            else:
+                attn = tensor_op.causal_attention_prefill(q, k_all, v_all)
         else:
             cache.get_svd(k, layer_idx=layer_idx)
             q, k = self.apply_rotary_pos_emb(q, k, position_ids)
             cache.prefill_kv_cache(v, layer_idx, k, q[:, :, -1:])
-            attn = tensor_op.causal_attention_prefill(q, k, v)
+            if self.minference:
+                attn = tensor_op.minference_prefill_kernel(q, k, v, self.minference_parttern[layer_idx])
+            else:
+                attn = tensor_op.causal_attention_prefill(q, k, v)
         del q, k, v
         attn = attn.reshape(bsz, q_len, self.hidden_size)
         if bsz * q_len <= 64 * 1024:

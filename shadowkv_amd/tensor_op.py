@@ -8,8 +8,8 @@ Names, argument order and return values follow the reference so `models/llama.py
 plus what replaces third-party CUDA packages on this path:
   sparse_attention_decode  (flash_attn_with_kvcache at base.py:341, q_len == 1)
   causal_attention_prefill (flash_attn_with_kvcache(causal=True) at base.py:293 / :311, the prompt)
+  minference_prefill_kernel (MInference vertical + slash sparse prefill, tensor_op.py:68-117)
   silu_and_mul, rotary_embedding_neox  (vllm._custom_ops at llama.py:296,421)
-`minference_prefill_kernel` (MInference sparse prefill) is outside the decode path and raises.
 """
 import math
 
@@ -364,8 +364,194 @@ def chunk_stats(k_ctx, chunk_size=8):
     return means, min_cos
 
 
-def minference_prefill_kernel(*args, **kwargs):
-    raise NotImplementedError("MInference sparse prefill is outside the decode hot path (SURVEY.md section 2a)")
+# ---------------------------------------------------------------------------- MInference sparse prefill
+MINFERENCE_TYPES = ("vertical_and_slash", "stream_llm")      # "block_sparse" is refused
+VS_SINKS, VS_LOCAL = 30, 100          # columns / diagonal offsets the estimate always keeps
+VS_MIN_VERTICAL, VS_MIN_SLASH = 30, 50
+INDEX_PAD = 2 ** 31 - 1               # list padding: entries outside [0, L) are ignored by the kernel
+
+
+def _check_prompt_qkv(q, k, v=None):
+    if q.dim() != 4 or k.dim() != 4 or (v is not None and v.dim() != 4):
+        raise ValueError("q must be [bs, Hq, L, D], k / v [bs, Hkv, L, D]")
+    bs, Hq, L, D = q.shape
+    Hkv = k.shape[1]
+    if k.shape[0] != bs or k.shape[2] != L or k.shape[3] != D or (v is not None and v.shape != k.shape):
+        raise ValueError(f"k {tuple(k.shape)} / v do not match q {tuple(q.shape)} (the sparse prefill needs kv_len == q_len)")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"{Hq} query heads are not a multiple of {Hkv} KV heads")
+    ts = (q, k) if v is None else (q, k, v)
+    if any(t.dtype != torch.bfloat16 or not t.is_cuda for t in ts):
+        raise ValueError("q / k / v must be bf16 tensors on the GPU")
+    for name, t in zip("qkv", ts):
+        if t.stride(3) != 1 or any(st % 8 for st in _row_strides(t)) or t.data_ptr() % 16:
+            raise ValueError(f"{name} must have a contiguous last dimension, strides that are multiples of 8 elements and a "
+                             "16-byte aligned start")
+    return bs, Hq, Hkv, L, D
+
+
+def _row_strides(t):            # (a size-1 dimension's stride is never followed: 0 keeps it out of the alignment check)
+    return [st if n > 1 else 0 for n, st in zip(t.shape[:3], t.stride()[:3])]
+
+
+def vertical_slash_scores(q, k):
+    """The vertical + slash estimate (tensor_op.py:86-101 of the reference, restated in DESIGN.md section 9), one native pair
+    of launches for every (sequence, query head): from the last m = min(64, L) queries, A = q k^T WITHOUT the 1 / sqrt(D)
+    scale, causal, P = softmax in f32; returns (c [bs, Hq, L], d [bs, Hq, L]) f32 with c[j] = sum_r P[r, j] (+inf for j < 30)
+    and d[s] = sum_r P[r, r - s] (+inf for s < 100).  q [bs, Hq, L, D], k [bs, Hkv, L, D] views (last dimension contiguous).
+    Deterministic: the same inputs give bit-identical scores."""
+    bs, Hq, Hkv, L, D = _check_prompt_qkv(q, k)
+    c = torch.empty(bs, Hq, L, dtype=torch.float32, device=q.device)
+    d = torch.empty_like(c)
+    ws = torch.empty(max(1, lib().skv_vs_estimate_workspace_bytes(bs, Hq, L)), dtype=torch.uint8, device=q.device)
+    check(lib().skv_vs_estimate(ptr(q), ptr(k), ptr(c), ptr(d), ptr(ws), bs, Hq, Hkv, L, L, D, *_row_strides(q),
+                                *_row_strides(k), current_stream_handle()), "vs_estimate")
+    return c, d
+
+
+def _per_head(x, Hq, what):
+    if isinstance(x, int):
+        return [x] * Hq
+    x = [int(v) for v in x]
+    if len(x) != Hq:
+        raise ValueError(f"{what}: {len(x)} per-head sizes for {Hq} query heads")
+    return x
+
+
+def _top_sorted(score, counts):
+    """score [bs, Hq, L]; counts: per-head list -> int32 [bs, Hq, max(counts)], each row the top counts[h] indices in
+    ascending order, padded with INDEX_PAD (torch.topk, as the reference)."""
+    kmax = max(counts)
+    idx = torch.topk(score, kmax, dim=-1).indices.to(torch.int32)
+    cnt = torch.tensor(counts, dtype=torch.int64, device=score.device).view(1, -1, 1)
+    keep = torch.arange(kmax, device=score.device).view(1, 1, -1) < cnt
+    idx = torch.where(keep, idx, torch.full_like(idx, INDEX_PAD))
+    return torch.sort(idx, dim=-1).values
+
+
+def vertical_slash_indices(q, k, vertical_size, slash_size, scores=None):
+    """The "vertical_and_slash" index sets: (vertical_idx, slash_idx) int32 [bs, Hq, n], each row ascending and padded with
+    INDEX_PAD.  Head h keeps the top min(L, max(vertical_size[h], 30)) columns by c and the top min(L, max(slash_size[h],
+    50)) diagonal offsets by d (vertical_slash_scores; pass `scores` = (c, d) to reuse them).  vertical_size / slash_size:
+    an int or one value per query head."""
+    bs, Hq, L = q.shape[0], q.shape[1], q.shape[2]
+    vs = [min(L, max(n, VS_MIN_VERTICAL)) for n in _per_head(vertical_size, Hq, "vertical_size")]
+    ss = [min(L, max(n, VS_MIN_SLASH)) for n in _per_head(slash_size, Hq, "slash_size")]
+    c, d = vertical_slash_scores(q, k) if scores is None else scores
+    return _top_sorted(c, vs), _top_sorted(d, ss)
+
+
+def _fixed_sets(counts, L, bs, device):
+    """stream_llm: [bs, Hq, max(counts)] int32 rows 0 .. counts[h] - 1, INDEX_PAD behind (entries >= L are ignored)."""
+    kmax = max(counts)
+    ar = torch.arange(kmax, dtype=torch.int32, device=device).view(1, 1, -1)
+    cnt = torch.tensor(counts, dtype=torch.int32, device=device).view(1, -1, 1)
+    return torch.where(ar < cnt, ar, torch.full_like(ar, INDEX_PAD)).expand(bs, -1, -1).contiguous()
+
+
+def _index_rows(idx, bs, Hq, device):
+    if not torch.is_tensor(idx):
+        idx = torch.tensor(idx, device=device)
+    if idx.dim() == 2:
+        idx = idx.unsqueeze(0).expand(bs, -1, -1)
+    if idx.dim() != 3 or idx.shape[0] != bs or idx.shape[1] != Hq or idx.shape[2] < 1:
+        raise ValueError(f"index lists must be [bs, Hq, n] or [Hq, n] with n >= 1, got {tuple(idx.shape)}")
+    if idx.dtype not in (torch.int32, torch.int64) or idx.device != torch.device(device):
+        raise ValueError("index lists must be int32 / int64 tensors on q's device")
+    return idx
+
+
+def sparse_prefill_attention(q, k, v, vertical_idx, slash_idx, out=None, sorted=False):
+    """Vertical + slash sparse causal attention, two native launches for every (sequence, query head):
+    row i (block b = i // 64, e = 64 (b + 1)) attends key j <= i iff j is a vertical column or lies in the window
+    [max(e - s, 64) - 64, max(e - s, 64)) of a slash offset s < e; softmax(q.k / sqrt(D)) over those keys times V.
+    q [bs, Hq, L, D], k / v [bs, Hkv, L, D] views; vertical_idx / slash_idx [bs, Hq, n] (or [Hq, n]) integer lists in any
+    order, duplicates allowed, entries outside [0, L) ignored; sorted=True promises int32 rows already ascending.
+    Returns [bs, L, Hq, D] (a reshape to [bs, L, Hq * D] is free).  bf16, D = 128."""
+    bs, Hq, Hkv, L, D = _check_prompt_qkv(q, k, v)
+    vi = _index_rows(vertical_idx, bs, Hq, q.device)
+    si = _index_rows(slash_idx, bs, Hq, q.device)
+    if not sorted:
+        # int64 entries beyond int32 are outside [0, L) either way
+        vi = torch.sort(vi.clamp(-1, INDEX_PAD).to(torch.int32), dim=-1).values
+        si = torch.sort(si.clamp(-1, INDEX_PAD).to(torch.int32), dim=-1).values
+    elif vi.dtype != torch.int32 or si.dtype != torch.int32:
+        raise ValueError("sorted=True needs int32 index lists")
+    vi, si = vi.contiguous(), si.contiguous()
+    if out is None:
+        out = torch.empty(bs, L, Hq, D, dtype=q.dtype, device=q.device)
+    elif out.shape != (bs, L, Hq, D) or not out.is_contiguous() or out.dtype != q.dtype:
+        raise ValueError("out must be a contiguous [bs, L, Hq, D] tensor of q's dtype")
+    ws = torch.empty(max(1, lib().skv_vs_attention_workspace_bytes(bs, Hq, L)), dtype=torch.uint8, device=q.device)
+    check(lib().skv_vs_sparse_attention(ptr(q), ptr(k), ptr(v), ptr(out), ptr(vi), ptr(si), ptr(ws), bs, Hq, Hkv, L, L, D,
+                                        vi.shape[-1], si.shape[-1], *_row_strides(q), *_row_strides(k), *_row_strides(v),
+                                        1.0 / math.sqrt(D), current_stream_handle()), "vs_sparse_attention")
+    return out
+
+
+def validate_minference_layer(pattern, Hq, where="pattern"):
+    """{head: (type, vertical_size, slash_size, score)} -> the same dict with int heads and tuple values; ValueError for a
+    head outside [0, Hq), an unknown or unsupported type, or a size that is not a positive integer."""
+    if not isinstance(pattern, dict):
+        raise ValueError(f"{where}: expected a dict {{head: [type, vertical_size, slash_size, score]}}")
+    out = {}
+    for head, entry in pattern.items():
+        try:
+            h = int(head)
+        except (TypeError, ValueError):
+            raise ValueError(f"{where}: head id {head!r} is not an integer") from None
+        if not 0 <= h < Hq:
+            raise ValueError(f"{where}, head {h}: head id outside [0, {Hq})")
+        if not isinstance(entry, (list, tuple)) or len(entry) != 4:
+            raise ValueError(f"{where}, head {h}: expected [type, vertical_size, slash_size, score], got {entry!r}")
+        ty, vsz, ssz, score = entry
+        if ty == "block_sparse":
+            raise ValueError(f"{where}, head {h}: 'block_sparse' is not supported (DESIGN.md section 9)")
+        if ty not in MINFERENCE_TYPES:
+            raise ValueError(f"{where}, head {h}: unknown pattern type {ty!r}")
+        for name, n in (("vertical_size", vsz), ("slash_size", ssz)):
+            if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+                raise ValueError(f"{where}, head {h}: {name} must be a positive integer, got {n!r}")
+        out[h] = (ty, vsz, ssz, score)
+    return out
+
+
+def minference_index_sets(query_states, key_states, minference_parttern):
+    """The per-head (vertical_idx, slash_idx) lists of one layer (sorted int32, INDEX_PAD behind): "vertical_and_slash"
+    heads from the estimate (one pair of launches for all heads, only when some head needs it), "stream_llm" heads the fixed
+    sets {0 .. vertical_size - 1} and {0 .. slash_size - 1}."""
+    bs, Hq, L = query_states.shape[0], query_states.shape[1], query_states.shape[2]
+    pat = validate_minference_layer(minference_parttern, Hq)
+    if len(pat) != Hq:
+        raise ValueError(f"the layer pattern names {len(pat)} of {Hq} query heads")
+    types = [pat[h][0] for h in range(Hq)]
+    vsz = [pat[h][1] for h in range(Hq)]
+    ssz = [pat[h][2] for h in range(Hq)]
+    dev = query_states.device
+    fixed_v, fixed_s = _fixed_sets(vsz, L, bs, dev), _fixed_sets(ssz, L, bs, dev)
+    if all(t == "stream_llm" for t in types):
+        return fixed_v, fixed_s
+    est_v, est_s = vertical_slash_indices(query_states, key_states, vsz, ssz)
+    stream = torch.tensor([t == "stream_llm" for t in types], device=dev).view(1, -1, 1)
+
+    def pick(est, fixed):
+        n = max(est.shape[-1], fixed.shape[-1])
+        est = F.pad(est, (0, n - est.shape[-1]), value=INDEX_PAD)
+        fixed = F.pad(fixed, (0, n - fixed.shape[-1]), value=INDEX_PAD)
+        return torch.where(stream, fixed, est).contiguous()
+
+    return pick(est_v, fixed_v), pick(est_s, fixed_s)
+
+
+def minference_prefill_kernel(query_states, key_states, value_states, minference_parttern):
+    """The reference's minference_prefill_kernel (tensor_op.py:68-117): q [bs, Hq, L, D], k / v [bs, Hkv, L, D] (kv_len ==
+    q_len: a prompt), minference_parttern {head: (type, vertical_size, slash_size, score)} for every query head of the layer.
+    Every head runs in the same launches (index estimate, then the sparse attention).  Returns [bs, L, Hq * D] contiguous."""
+    bs, Hq, L, D = query_states.shape
+    assert L > 1
+    vi, si = minference_index_sets(query_states, key_states, minference_parttern)
+    out = sparse_prefill_attention(query_states, key_states, value_states, vi, si, sorted=True)
+    return out.view(bs, L, Hq * D)
 
 
 # ---------------------------------------------------------------------------- sampling (tensor_op.py:242-297)
