@@ -11,13 +11,14 @@
 //     the P tile of keys 64 t .. + 63 (column sums -> c) and of the 128 keys that offsets 64 t .. + 63 touch (diagonal
 //     sums -> d), each through LDS.
 //   Score tiles: 4 waves, wave w = (query half w & 1, key half w >> 1); S^T = K.Q^T on v_mfma_f32_32x32x16_bf16 with the Q
-//   fragments in registers (the layout of skv_prefill_attn.hip) and K read straight from global memory.
+//   fragments in registers (the layout of skv_flash_tile.h) and K read straight from global memory.
 //
 // Sparse attention (two launches):
 //   launch 1 (vs_bitmap): one bit per (sequence, query head, slash offset in [0, L)), so the attention can ask "does a
 //     window of this block cover column v" with at most five word reads; zeroed and set by one workgroup per head.
 //   launch 2 (vs_attn): workgroup = 64 query rows (one mask block b, e = 64 (b + 1)) of one (sequence, query head), 2 waves
-//     of 32 rows; the Q / K / V / online-softmax structure of skv_prefill_attn.hip.  Key tiles of 64 come from
+//     of 32 rows; the tile body (Q / K / V layouts, online softmax, P.V) is skv_flash_tile.h, with CAN_BE_EMPTY = true: a
+//     row may attend no key of a tile, or none at all (it then writes zeros).  Key tiles of 64 come from
 //       - the slash windows of the block, merged on the fly from the head's ascending offset list into contiguous ranges
 //         (windows with ascending s have descending ends) and cut from the top into tiles [max(lo, top - 64), top);
 //       - then 64 consecutive entries of the head's ascending vertical list below min(e, L), minus duplicates and minus
@@ -26,40 +27,26 @@
 //     wave's first row skip the mask.  The next tile's rows are loaded under the current tile's MFMAs.  The grid runs the
 //     last (heaviest) blocks first.
 #include "../../include/shadowkv_hip.h"
-#include "skv_common.h"
+#include "skv_flash_tile.h"
 
 #include <limits.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 vs_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float vs_f32x16;
 typedef __attribute__((ext_vector_type(4))) int vs_i32x4;
 
-#define VS_D 128
 #define VS_LASTQ 64          // queries of the estimate
 #define VS_CHUNK 2048        // keys per row-statistics workgroup
-#define VS_KB 64             // keys per tile
-#define VS_KP (VS_D + 8)     // K LDS row pitch, bf16
-#define VS_VP (VS_KB + 8)    // V^T LDS row pitch, bf16
-#define VS_PP (2 * VS_KB + 4) // P LDS row pitch, f32
+#define VS_PP (2 * FT_KB + 4) // P LDS row pitch, f32
 #define VS_SINKS 30
 #define VS_LOCAL 100
 
-__device__ __forceinline__ int vs_crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// Q fragments of query row L - m + qrow (zero when qrow >= m): the B operand of S^T = K.Q^T
-__device__ __forceinline__ void vs_load_q(vs_bf16x8 (&qf)[8], const bf16_t* qh, long long qss, int L, int m, int qrow, int h) {
+// Q fragments of query row L - m + qrow (zero when qrow >= m)
+__device__ __forceinline__ void vs_load_q(ft_bf16x8 (&qf)[8], const bf16_t* qh, long long qss, int L, int m, int qrow, int h) {
     const bool ok = qrow < m;
-    const bf16_t* qp = qh + (long long)(L - m + (ok ? qrow : 0)) * qss + 8 * h;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        u32x4 w = *reinterpret_cast<const u32x4*>(qp + 16 * s);
-        if (!ok) w = (u32x4){0u, 0u, 0u, 0u};
-        qf[s] = __builtin_bit_cast(vs_bf16x8, w);
-    }
+    ft_load_q(qf, qh + (long long)(L - m + (ok ? qrow : 0)) * qss, ok, h);
 }
 
 // S^T[key][query] for keys key0 + crow(i, h) (K rows read from global, zero outside [0, L)): 32 keys x 32 queries
-__device__ __forceinline__ vs_f32x16 vs_scores32(const vs_bf16x8 (&qf)[8], const bf16_t* kh, long long kss, int L, int key0,
+__device__ __forceinline__ ft_f32x16 vs_scores32(const ft_bf16x8 (&qf)[8], const bf16_t* kh, long long kss, int L, int key0,
                                                  int r, int h) {
     const int key = key0 + r;
     const bool ok = key >= 0 && key < L;
@@ -70,10 +57,10 @@ __device__ __forceinline__ vs_f32x16 vs_scores32(const vs_bf16x8 (&qf)[8], const
         kw[s] = *reinterpret_cast<const u32x4*>(kp + 16 * s);
         if (!ok) kw[s] = (u32x4){0u, 0u, 0u, 0u};
     }
-    vs_f32x16 sc = (vs_f32x16){};
+    ft_f32x16 sc = (ft_f32x16){};
 #pragma unroll
     for (int s = 0; s < 8; ++s)
-        sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(vs_bf16x8, kw[s]), qf[s], sc, 0, 0, 0);
+        sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ft_bf16x8, kw[s]), qf[s], sc, 0, 0, 0);
     return sc;
 }
 
@@ -89,19 +76,19 @@ __global__ __launch_bounds__(256) void vs_rowstat_kernel(const bf16_t* __restric
     const int b = bh / Hq, hq = bh - b * Hq;
     const int m = min(VS_LASTQ, L);
     const int qrow = 32 * qhalf + r, rabs = L - m + qrow;
-    vs_bf16x8 qf[8];
+    ft_bf16x8 qf[8];
     vs_load_q(qf, q + (long long)b * qsb + (long long)hq * qsh, qss, L, m, qrow, h);
     const bf16_t* kh = k + (long long)b * ksb + (long long)(hq / G) * ksh;
     const float LOG2E = 1.44269504088896341f;
     float mx = -INFINITY, sm = 0.f;
     const int k_end = min(L, (chunk + 1) * VS_CHUNK);
-    for (int key0 = chunk * VS_CHUNK; key0 < k_end; key0 += VS_KB) {
+    for (int key0 = chunk * VS_CHUNK; key0 < k_end; key0 += FT_KB) {
         const int kb = key0 + 32 * khalf;
-        vs_f32x16 sc = vs_scores32(qf, kh, kss, L, kb, r, h);
+        ft_f32x16 sc = vs_scores32(qf, kh, kss, L, kb, r, h);
         float mt = -INFINITY;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int key = kb + vs_crow(i, h);
+            const int key = kb + ft_crow(i, h);
             const float x = (key <= rabs && key < L) ? sc[i] * LOG2E : -INFINITY;
             sc[i] = x;
             mt = fmaxf(mt, x);
@@ -169,7 +156,7 @@ __global__ __launch_bounds__(256) void vs_scores_kernel(const bf16_t* __restrict
         s_mx[tid] = mx;
         s_inv[tid] = l > 0.f ? 1.0f / l : 0.f;
     }
-    vs_bf16x8 qf[8];
+    ft_bf16x8 qf[8];
     vs_load_q(qf, q + (long long)b * qsb + (long long)hq * qsh, qss, L, m, qrow, h);
     const bf16_t* kh = k + (long long)b * ksb + (long long)(hq / G) * ksh;
     __syncthreads();
@@ -178,32 +165,32 @@ __global__ __launch_bounds__(256) void vs_scores_kernel(const bf16_t* __restrict
     // P[qrow][c0 + key offset] into s_p[qrow][slot0 + key offset] for the 64 keys key0 .. key0 + 63
     auto p_tile = [&](int key0, int slot0) {
         const int kb = key0 + 32 * khalf;
-        const vs_f32x16 sc = vs_scores32(qf, kh, kss, L, kb, r, h);
+        const ft_f32x16 sc = vs_scores32(qf, kh, kss, L, kb, r, h);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int key = kb + vs_crow(i, h);
+            const int key = kb + ft_crow(i, h);
             const bool ok = qrow < m && key >= 0 && key <= rabs && key < L;
-            s_p[qrow * VS_PP + slot0 + 32 * khalf + vs_crow(i, h)] = ok ? __builtin_amdgcn_exp2f(sc[i] * LOG2E - rmx) * rinv : 0.f;
+            s_p[qrow * VS_PP + slot0 + 32 * khalf + ft_crow(i, h)] = ok ? __builtin_amdgcn_exp2f(sc[i] * LOG2E - rmx) * rinv : 0.f;
         }
     };
 
-    const int s0 = VS_KB * t;
+    const int s0 = FT_KB * t;
     p_tile(s0, 0);                              // columns 64 t .. + 63
     __syncthreads();
-    if (tid < VS_KB && s0 + tid < L) {
+    if (tid < FT_KB && s0 + tid < L) {
         float acc = 0.f;
         for (int i = 0; i < VS_LASTQ; ++i) acc += s_p[i * VS_PP + tid];
         col[(long long)bh * L + s0 + tid] = (s0 + tid < VS_SINKS) ? INFINITY : acc;
     }
     __syncthreads();
     // offsets s0 + si: row qrow meets key L - m + qrow - s0 - si = base + 64 + qrow - si, base = L - m - s0 - 64
-    const int base = L - m - s0 - VS_KB;
+    const int base = L - m - s0 - FT_KB;
     p_tile(base, 0);
-    p_tile(base + VS_KB, VS_KB);
+    p_tile(base + FT_KB, FT_KB);
     __syncthreads();
-    if (tid < VS_KB && s0 + tid < L) {
+    if (tid < FT_KB && s0 + tid < L) {
         float acc = 0.f;
-        for (int i = 0; i < VS_LASTQ; ++i) acc += s_p[i * VS_PP + VS_KB + i - tid];
+        for (int i = 0; i < VS_LASTQ; ++i) acc += s_p[i * VS_PP + FT_KB + i - tid];
         diag[(long long)bh * L + s0 + tid] = (s0 + tid < VS_LOCAL) ? INFINITY : acc;
     }
 }
@@ -240,9 +227,9 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
     const int* __restrict__ vert, const int* __restrict__ slash, const uint32_t* __restrict__ bits, int Hq, int G, int L,
     int n_vert, int n_slash, int words, long long qsb, long long qsh, long long qss, long long ksb, long long ksh,
     long long kss, long long vsb, long long vsh, long long vss, float scale_log2, int n_blk) {
-    __shared__ __attribute__((aligned(16))) bf16_t s_k[VS_KB * VS_KP];
-    __shared__ __attribute__((aligned(16))) bf16_t s_vt[VS_D * VS_VP];
-    __shared__ __attribute__((aligned(16))) int s_kid[VS_KB];
+    __shared__ __attribute__((aligned(16))) bf16_t s_k[FT_KB * FT_KP];
+    __shared__ __attribute__((aligned(16))) bf16_t s_vt[FT_D * FT_VP];
+    __shared__ __attribute__((aligned(16))) int s_kid[FT_KB];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -250,22 +237,14 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
     const int bh = (int)(blockIdx.x % (unsigned)nbh);
     const int blk = n_blk - 1 - (int)(blockIdx.x / (unsigned)nbh);     // last (heaviest) block first
     const int b = bh / Hq, hq = bh - b * Hq, hk = hq / G;
-    const int e = VS_KB * (blk + 1);
+    const int e = FT_KB * (blk + 1);
     const int lim = min(e, L);                                         // list entries >= lim do nothing for this block
-    const int qw = VS_KB * blk + 32 * wave, qi = qw + r;
+    const int qw = FT_KB * blk + 32 * wave, qi = qw + r;
     const bool row_ok = qi < L, wave_on = qw < L;
     const int wave_hi = min(qw + 31, L - 1);
 
-    vs_bf16x8 qf[8];
-    {
-        const bf16_t* qp = q + (long long)b * qsb + (long long)hq * qsh + (long long)min(qi, L - 1) * qss + 8 * h;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            u32x4 w = *reinterpret_cast<const u32x4*>(qp + 16 * s);
-            if (!row_ok) w = (u32x4){0u, 0u, 0u, 0u};
-            qf[s] = __builtin_bit_cast(vs_bf16x8, w);
-        }
-    }
+    ft_bf16x8 qf[8];
+    ft_load_q(qf, q + (long long)b * qsb + (long long)hq * qsh + (long long)min(qi, L - 1) * qss, row_ok, h);
     const bf16_t* kb = k + (long long)b * ksb + (long long)hk * ksh;
     const bf16_t* vb = v + (long long)b * vsb + (long long)hk * vsh;
     const int* sl = slash + (long long)bh * n_slash;
@@ -281,16 +260,16 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
     auto next_tile = [&](int& kind, int& start, int& cnt) {
         for (;;) {
             // absorb the next windows while they touch what is due or emitted and a full tile is not yet due
-            while (sp < n_slash && cov > top - VS_KB) {
+            while (sp < n_slash && cov > top - FT_KB) {
                 const int s = sl[sp];
                 if (s >= lim) { sp = n_slash; break; }
-                const int hi = max(e - s, VS_KB);
+                const int hi = max(e - s, FT_KB);
                 if (hi < cov) break;                                   // a gap: the window starts a new range
-                cov = min(cov, hi - VS_KB);
+                cov = min(cov, hi - FT_KB);
                 ++sp;
             }
             if (cov < top) {
-                start = max(cov, top - VS_KB);
+                start = max(cov, top - FT_KB);
                 cnt = top - start;
                 top = start;
                 kind = 1;
@@ -299,8 +278,8 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
             if (sp < n_slash) {                                        // a new range below everything emitted
                 const int s = sl[sp];
                 if (s < lim) {
-                    top = max(e - s, VS_KB);
-                    cov = top - VS_KB;
+                    top = max(e - s, FT_KB);
+                    cov = top - FT_KB;
                     ++sp;
                     continue;
                 }
@@ -310,7 +289,7 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
                 kind = 2;
                 start = vp;
                 cnt = 0;
-                vp += VS_KB;
+                vp += FT_KB;
                 return;
             }
             kind = 0;
@@ -318,8 +297,6 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
         }
     };
 
-    // staging: thread t moves rows 2 p, 2 p + 1 (p = (t >> 4) + 8 i, i = 0 .. 3) of chunk c = t & 15
-    const int st_c = tid & 15;
     u32x4 kr[4][2], vr[4][2];
     int kid_next = INT_MAX;                                            // key id of row tid of the next tile (tid < 64)
     auto tile_key = [&](int kind, int start, int cnt, int row) -> int {
@@ -330,30 +307,16 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
         return (x >= 0 && x < lim) ? x : INT_MAX;
     };
     auto load_tile = [&](int kind, int start, int cnt) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int p = (tid >> 4) + 8 * i;
-#pragma unroll
-            for (int e2 = 0; e2 < 2; ++e2) {
-                const int key = tile_key(kind, start, cnt, 2 * p + e2);
-                u32x4 a = {0u, 0u, 0u, 0u}, c = {0u, 0u, 0u, 0u};
-                if (key < L) {
-                    a = *reinterpret_cast<const u32x4*>(kb + (long long)key * kss + 8 * st_c);
-                    c = *reinterpret_cast<const u32x4*>(vb + (long long)key * vss + 8 * st_c);
-                }
-                kr[i][e2] = a;
-                vr[i][e2] = c;
-            }
-        }
-        if (tid < VS_KB) {
+        ft_load_tile<128>(kr, vr, kb, vb, kss, vss, L, tid, [&](int row) { return tile_key(kind, start, cnt, row); });
+        if (tid < FT_KB) {
             int key = tile_key(kind, start, cnt, tid);
             if (kind == 2 && key != INT_MAX) {
                 // a duplicate of the previous entry, or a column some window of this block covers, is not gathered again
                 const int i = start + tid;
                 if (i > 0 && vl[i - 1] == key) key = INT_MAX;
                 else {
-                    const int lo = max(0, e - key - VS_KB);
-                    const int hi = min(L - 1, key < VS_KB ? e - 1 : e - key - 1);
+                    const int lo = max(0, e - key - FT_KB);
+                    const int hi = min(L - 1, key < FT_KB ? e - 1 : e - key - 1);
                     if (lo <= hi && vs_any_bit(bw, lo, hi)) key = INT_MAX;
                 }
             }
@@ -361,26 +324,13 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
         }
     };
     auto store_tile = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int p = (tid >> 4) + 8 * i;
-#pragma unroll
-            for (int e2 = 0; e2 < 2; ++e2) *reinterpret_cast<u32x4*>(&s_k[(2 * p + e2) * VS_KP + 8 * st_c]) = kr[i][e2];
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const uint32_t x0 = vr[i][0][w], x1 = vr[i][1][w];
-                const uint32_t lo = (x0 & 0xffffu) | (x1 << 16);
-                const uint32_t hi = (x0 >> 16) | (x1 & 0xffff0000u);
-                *reinterpret_cast<uint32_t*>(&s_vt[(8 * st_c + 2 * w) * VS_VP + 2 * p]) = lo;
-                *reinterpret_cast<uint32_t*>(&s_vt[(8 * st_c + 2 * w + 1) * VS_VP + 2 * p]) = hi;
-            }
-        }
-        if (tid < VS_KB) s_kid[tid] = kid_next;
+        ft_store_tile<128>(s_k, s_vt, kr, vr, tid);
+        if (tid < FT_KB) s_kid[tid] = kid_next;
     };
 
-    vs_f32x16 o[4];
+    ft_f32x16 o[4];
 #pragma unroll
-    for (int d = 0; d < 4; ++d) o[d] = (vs_f32x16){};
+    for (int d = 0; d < 4; ++d) o[d] = (ft_f32x16){};
     float m = -INFINITY, l = 0.f;
 
     int kind, start, cnt;
@@ -397,26 +347,11 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
         const int tmin = cur_kind == 1 ? cur_start : vl[cur_start];
         if (!wave_on || tmin > wave_hi) continue;
 
-        vs_f32x16 sc[2];
-#pragma unroll
-        for (int kb2 = 0; kb2 < 2; ++kb2) {
-            sc[kb2] = (vs_f32x16){};
-            const bf16_t* kp = &s_k[(32 * kb2 + r) * VS_KP + 8 * h];
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-                sc[kb2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                    __builtin_bit_cast(vs_bf16x8, *reinterpret_cast<const u32x4*>(kp + 16 * s)), qf[s], sc[kb2], 0, 0, 0);
-        }
+        ft_f32x16 sc[2];
+        ft_scores_from_lds(sc, s_k, qf, r, h);
         float mt = -INFINITY;
-        if (cur_kind == 1 && cur_cnt == VS_KB && cur_start + VS_KB - 1 <= qw) {   // full window tile below every row
-#pragma unroll
-            for (int kb2 = 0; kb2 < 2; ++kb2)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float x = sc[kb2][i] * scale_log2;
-                    sc[kb2][i] = x;
-                    mt = fmaxf(mt, x);
-                }
+        if (cur_kind == 1 && cur_cnt == FT_KB && cur_start + FT_KB - 1 <= qw) {   // full window tile below every row
+            mt = ft_scale_unmasked(sc, scale_log2);
         } else {
 #pragma unroll
             for (int kb2 = 0; kb2 < 2; ++kb2)
@@ -425,79 +360,21 @@ __global__ __launch_bounds__(128) void vs_attn_kernel(
                     const vs_i32x4 id = *reinterpret_cast<const vs_i32x4*>(&s_kid[32 * kb2 + 8 * g + 4 * h]);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const int i = 4 * g + j;      // vs_crow(i, h) = 8 g + 4 h + j
+                        const int i = 4 * g + j;      // ft_crow(i, h) = 8 g + 4 h + j
                         const float x = id[j] <= qi ? sc[kb2][i] * scale_log2 : -INFINITY;
                         sc[kb2][i] = x;
                         mt = fmaxf(mt, x);
                     }
                 }
         }
-        mt = fmaxf(mt, __shfl_xor(mt, 32));
-        const float m_new = fmaxf(m, mt);
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;        // a row with no key yet: every weight stays 0
-        const float alpha = __builtin_amdgcn_exp2f(m - m_use);
-        m = m_new;
-        float rs = 0.f;
-        uint32_t pk[2][8];
-#pragma unroll
-        for (int kb2 = 0; kb2 < 2; ++kb2)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                const float p0 = __builtin_amdgcn_exp2f(sc[kb2][i] - m_use);
-                const float p1 = __builtin_amdgcn_exp2f(sc[kb2][i + 1] - m_use);
-                rs += p0;
-                rs += p1;
-                pk[kb2][i >> 1] = pack_bf2(p0, p1);
-            }
-        l = l * alpha + rs;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) o[d][i] *= alpha;
-#pragma unroll
-        for (int kb2 = 0; kb2 < 2; ++kb2)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const vs_bf16x8 pb = __builtin_bit_cast(
-                    vs_bf16x8, (u32x4){pk[kb2][4 * s], pk[kb2][4 * s + 1], pk[kb2][4 * s + 2], pk[kb2][4 * s + 3]});
-                const int kc = 32 * kb2 + 16 * s + 4 * h;
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const bf16_t* vp2 = &s_vt[(32 * d + r) * VS_VP + kc];
-                    const u32x2 a0 = *reinterpret_cast<const u32x2*>(vp2);
-                    const u32x2 a1 = *reinterpret_cast<const u32x2*>(vp2 + 8);
-                    const vs_bf16x8 va = __builtin_bit_cast(vs_bf16x8, (u32x4){a0[0], a0[1], a1[0], a1[1]});
-                    o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pb, o[d], 0, 0, 0);
-                }
-            }
+        ft_softmax_pv<true>(sc, mt, m, l, o, s_vt, r, h);
     }
 
     if (!row_ok) return;
-    l = l + __shfl_xor(l, 32);
-    const float inv = l > 0.f ? 1.0f / l : 0.f;                      // a row that attends no key writes zeros
-    bf16_t* op = out + (((long long)b * L + qi) * Hq + hq) * VS_D + 4 * h;
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const u32x2 w = {pack_bf2(o[d][4 * g] * inv, o[d][4 * g + 1] * inv),
-                             pack_bf2(o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv)};
-            *reinterpret_cast<u32x2*>(op + 32 * d + 8 * g) = w;
-        }
+    ft_write_out<true>(o, l, out + (((long long)b * L + qi) * Hq + hq) * FT_D, h);
 }
 
 // -------------------------------------------------------------------------------------------------------------- host
-static int vs_check_qk(const void* q, const void* k, int bs, int Hq, int Hkv, int q_len, int kv_len, int head_dim,
-                       const long long* strides, int n_strides) {
-    if (!q || !k) return SKV_ERR_ARG;
-    if (bs < 1 || Hq < 1 || Hkv < 1 || q_len < 1 || kv_len != q_len || Hq % Hkv) return SKV_ERR_ARG;
-    for (int i = 0; i < n_strides; ++i)
-        if (strides[i] % 8) return SKV_ERR_ARG;
-    if (((uintptr_t)q | (uintptr_t)k) % 16) return SKV_ERR_ARG;
-    if (head_dim != VS_D) return SKV_ERR_UNSUPPORTED;
-    return SKV_OK;
-}
-
 extern "C" long long skv_vs_estimate_workspace_bytes(int batch_size, int q_heads, int q_len) {
     if (batch_size < 1 || q_heads < 1 || q_len < 1) return 0;
     return (long long)batch_size * q_heads * ((q_len + VS_CHUNK - 1) / VS_CHUNK) * 2 * VS_LASTQ * (long long)sizeof(float);
@@ -512,12 +389,13 @@ extern "C" int skv_vs_estimate(const void* q, const void* k, void* col_score, vo
                                int batch_size, int q_heads, int kv_heads, int q_len, int kv_len, int head_dim,
                                long long q_stride_b, long long q_stride_h, long long q_stride_s, long long k_stride_b,
                                long long k_stride_h, long long k_stride_s, skv_stream_t stream) {
+    const void* const ptrs[2] = {q, k};
     const long long strides[6] = {q_stride_b, q_stride_h, q_stride_s, k_stride_b, k_stride_h, k_stride_s};
     if (!col_score || !diag_score || !workspace) return SKV_ERR_ARG;
-    const int rc = vs_check_qk(q, k, batch_size, q_heads, kv_heads, q_len, kv_len, head_dim, strides, 6);
+    const int rc = ft_check_attn_args(ptrs, 2, batch_size, q_heads, kv_heads, q_len, kv_len, false, head_dim, strides, 6);
     if (rc != SKV_OK) return rc;
     if (((uintptr_t)col_score | (uintptr_t)diag_score | (uintptr_t)workspace) % 4) return SKV_ERR_ARG;
-    const long long n_chunk = (q_len + VS_CHUNK - 1) / VS_CHUNK, n_tile = (q_len + VS_KB - 1) / VS_KB;
+    const long long n_chunk = (q_len + VS_CHUNK - 1) / VS_CHUNK, n_tile = (q_len + FT_KB - 1) / FT_KB;
     const long long nbh = (long long)batch_size * q_heads;
     if (nbh * n_tile > INT_MAX) return SKV_ERR_UNSUPPORTED;
     const int G = q_heads / kv_heads;
@@ -539,15 +417,16 @@ extern "C" int skv_vs_sparse_attention(const void* q, const void* k, const void*
                                        long long k_stride_b, long long k_stride_h, long long k_stride_s,
                                        long long v_stride_b, long long v_stride_h, long long v_stride_s, float scale,
                                        skv_stream_t stream) {
+    const void* const ptrs[2] = {q, k};
     const long long strides[9] = {q_stride_b, q_stride_h, q_stride_s, k_stride_b, k_stride_h,
                                   k_stride_s, v_stride_b, v_stride_h, v_stride_s};
     if (!v || !out || !vertical_idx || !slash_idx || !workspace) return SKV_ERR_ARG;
     if (n_vertical < 1 || n_slash < 1) return SKV_ERR_ARG;
-    const int rc = vs_check_qk(q, k, batch_size, q_heads, kv_heads, q_len, kv_len, head_dim, strides, 9);
+    const int rc = ft_check_attn_args(ptrs, 2, batch_size, q_heads, kv_heads, q_len, kv_len, false, head_dim, strides, 9);
     if (rc != SKV_OK) return rc;
     if (((uintptr_t)v | (uintptr_t)out) % 16) return SKV_ERR_ARG;
     if (((uintptr_t)vertical_idx | (uintptr_t)slash_idx | (uintptr_t)workspace) % 4) return SKV_ERR_ARG;
-    const long long n_blk = (q_len + VS_KB - 1) / VS_KB, nbh = (long long)batch_size * q_heads;
+    const long long n_blk = (q_len + FT_KB - 1) / FT_KB, nbh = (long long)batch_size * q_heads;
     if (nbh * n_blk > INT_MAX) return SKV_ERR_UNSUPPORTED;
     const int words = (q_len + 31) / 32;
     hipLaunchKernelGGL(vs_bitmap_kernel, dim3((unsigned)nbh), dim3(256), 0, (hipStream_t)stream, (const int*)slash_idx,
