@@ -292,6 +292,38 @@ SKV_EXPORT int skv_qkv_gemv_rope_update(const void* Wqkv, const void* x, const v
                              int K, int q_heads, int kv_heads, int head_dim, long long cos_sin_stride, int cos_sin_rows,
                              long long cache_stride_h, int cache_rows, int rope_mode, skv_stream_t stream);
 
+/* The fused QKV projection split by rows.  The landmark scan that follows the projection needs only q; the k and v rows
+ * (2 * kv_heads * 128 of the weight rows) produce the new token's cache row, which nothing reads before the fetch launch.
+ * skv_q_gemv_rope is skv_qkv_gemv_rope_update over the q rows alone (norm prologue, RoPE, q_out; h_out stored as there;
+ * K must be 4096, norm_weight non-NULL).  The k / v rows are then computed by extra workgroups of the layer's selection
+ * launches: skv_select_chunks_fused_kv_proj (below) with a skv_kv_proj_t that names the SAME weights, norm weight, bias,
+ * RoPE table, position and cache row, and as `h` the residual stream this launch stored in h_out (x itself where residual
+ * was NULL).  Every row is computed by the same lane -> element mapping, k-step order and reduction tree as in the one
+ * launch: q_out, h_out and the appended K / V rows are bit-identical to skv_qkv_gemv_rope_update's.  bs == 1. */
+SKV_EXPORT int skv_q_gemv_rope(const void* Wqkv, const void* x, const void* residual, const void* norm_weight, float eps,
+                    void* h_out, const void* bias, const void* cos_sin, const int64_t* pos, const void* q_override,
+                    void* q_out, int K, int q_heads, int kv_heads, int head_dim, long long cos_sin_stride, int cos_sin_rows,
+                    int rope_mode, skv_stream_t stream);
+
+/* the k / v rows of one token as a role of a selection launch; read on the host at the call, not retained */
+typedef struct skv_kv_proj {
+    const void* Wqkv;           /* [(q_heads + 2 kv_heads) * 128][4096] bf16 */
+    const void* h;              /* [4096] bf16: the hidden state the q launch normalised (its h_out) */
+    const void* norm_weight;    /* [4096] */
+    const void* bias;           /* nullable [(q_heads + 2 kv_heads) * 128] */
+    const void* cos_sin;
+    const int64_t* pos;         /* [1] RoPE position */
+    const int64_t* row_idx;     /* [1] cache row of the new token; outside [0, cache_rows): nothing is written */
+    void* k_cache;              /* [kv_heads][cache_rows][128] with cache_stride_h elements between heads */
+    void* v_cache;
+    long long cos_sin_stride, cache_stride_h;
+    float eps;
+    int K, q_heads, kv_heads, head_dim, cos_sin_rows, cache_rows, rope_mode;
+    int placement;              /* SKV_KV_PROJ_IN_SCAN: behind the scan's tiles; SKV_KV_PROJ_IN_TOPK: beside the top-k workgroups */
+} skv_kv_proj_t;
+#define SKV_KV_PROJ_IN_SCAN 0
+#define SKV_KV_PROJ_IN_TOPK 1
+
 /* ---- part 3b: in-place chunk layout (MI355X-first variant of parts 1-2) ---------------------------------------- */
 
 /* skv_select_chunks with an IN-PLACE resident set: chunks selected again keep their slot, the misses (ascending chunk
@@ -369,6 +401,14 @@ SKV_EXPORT int skv_select_chunks_fused(const void* q, const void* landmarks, con
                             int blocks, int groups, int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age,
                             float alpha, void* select_state, void* early_state, const void* v_host, long long host_block_stride,
                             int n_chunks, int early_max, float margin, skv_stream_t stream);
+/* skv_select_chunks_fused with the k / v projection role (skv_q_gemv_rope above) in one of its two launches: same selection
+ * results, same workspace contents; the new token's K / V row is complete when the second launch ends.  kv_proj NULL: exactly
+ * skv_select_chunks_fused.  K == 4096, head_dim == 128, rope_mode 1 or 2; other shapes: SKV_ERR_UNSUPPORTED. */
+SKV_EXPORT int skv_select_chunks_fused_kv_proj(const void* q, const void* landmarks, const int64_t* landmark_idx, int64_t* cached_pos_ids,
+                            int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts, void* workspace, int64_t* selected_out,
+                            int blocks, int groups, int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age,
+                            float alpha, void* select_state, void* early_state, const void* v_host, long long host_block_stride,
+                            int n_chunks, int early_max, float margin, const skv_kv_proj_t* kv_proj, skv_stream_t stream);
 
 /* ---- speculative early V fetch (in-place layout) -------------------------------------------------------------------
  * Which chunks a step will MISS is predictable as soon as the scan has produced the logits: a landmark slot whose logit

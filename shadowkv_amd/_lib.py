@@ -18,6 +18,18 @@ c_f = ctypes.c_float
 c_p = ctypes.c_void_p
 c_sz = ctypes.c_size_t
 
+
+
+class KvProjDesc(ctypes.Structure):
+    """skv_kv_proj_t: the k / v rows of the fused QKV projection as a role of a selection launch (read at the call)."""
+    _fields_ = [("Wqkv", c_p), ("h", c_p), ("norm_weight", c_p), ("bias", c_p), ("cos_sin", c_p), ("pos", c_p), ("row_idx", c_p),
+                ("k_cache", c_p), ("v_cache", c_p), ("cos_sin_stride", c_ll), ("cache_stride_h", c_ll), ("eps", c_f), ("K", c_int),
+                ("q_heads", c_int), ("kv_heads", c_int), ("head_dim", c_int), ("cos_sin_rows", c_int), ("cache_rows", c_int),
+                ("rope_mode", c_int), ("placement", c_int)]
+
+
+KV_PROJ_IN_SCAN, KV_PROJ_IN_TOPK = 0, 1
+
 _ROPE_PUSH = [c_p] * 5 + [c_int] * 19 + [c_p]
 
 _SIGS = {
@@ -49,6 +61,8 @@ _SIGS = {
     "skv_select_state_init": (c_int, [c_p, c_int, c_int, c_p]),
     "skv_score_landmarks_fused": (c_int, [c_p] * 4 + [c_int] * 3 + [c_f, c_p, c_p, c_int, c_int, c_p]),
     "skv_select_chunks_fused": (c_int, [c_p] * 9 + [c_int] * 5 + [c_p, c_f] + [c_p, c_p, c_p, c_ll, c_int, c_int, c_f, c_p]),
+    "skv_select_chunks_fused_kv_proj": (c_int, [c_p] * 9 + [c_int] * 5 + [c_p, c_f] + [c_p, c_p, c_p, c_ll, c_int, c_int, c_f,
+                                                ctypes.POINTER(KvProjDesc), c_p]),
     "skv_early_state_bytes": (c_sz, [c_int] * 5),
     "skv_early_state_offsets": (c_int, [c_int] * 5 + [ctypes.POINTER(c_ll)]),
     "skv_early_state_offsets2": (c_int, [c_int] * 5 + [ctypes.POINTER(c_ll), c_int]),
@@ -77,6 +91,7 @@ _SIGS = {
     "skv_norm_gemv_near_pull_bf16": (c_int, [c_p] * 4 + [c_f] + [c_p] * 2 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
     "skv_gemv_near_pull_bf16": (c_int, [c_p] * 4 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
     "skv_qkv_gemv_rope_update": (c_int, [c_p] * 4 + [c_f] + [c_p] * 9 + [c_int] * 4 + [c_ll, c_int, c_ll] + [c_int] * 2 + [c_p]),
+    "skv_q_gemv_rope": (c_int, [c_p] * 4 + [c_f] + [c_p] * 6 + [c_int] * 4 + [c_ll] + [c_int] * 2 + [c_p]),
     "skv_gemv_bf16": (c_int, [c_p] * 4 + [c_int] * 3 + [c_p]),
     "skv_chunk_stats": (c_int, [c_p, c_ll] + [c_int] * 4 + [c_p] * 3),
     "skv_host_alloc": (c_int, [ctypes.POINTER(c_p), c_sz]),

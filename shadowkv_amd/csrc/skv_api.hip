@@ -4,12 +4,14 @@
 #include "../../include/shadowkv_hip.h"
 #include "skv_common.h"
 #include "skv_launch.h"
+#include "skv_kvproj.h"
 
 #include <string.h>
 
 // launchers (defined in the kernel files)
 int skv_launch_score(const void* q, const void* lm, void* D, float* pmax, float* psum, int B, int G, int N,
-                     float alpha, hipStream_t st, const EarlyHooks* hooks = nullptr, const FusedSel* fused = nullptr);
+                     float alpha, hipStream_t st, const EarlyHooks* hooks = nullptr, const FusedSel* fused = nullptr,
+                     const KvProj* kv_proj = nullptr);
 int skv_launch_softmax_final_apply(const void* D, float* pmax, float* psum, void* P, int B, int m, int N,
                                    hipStream_t st);
 int skv_launch_normalize_groupmax(const void* D, const float* pmax, const float* psum, void* P, void* score,
@@ -20,7 +22,7 @@ int skv_launch_topk_reorder(const void* score, int score_stride, const int64_t* 
 int skv_launch_topk_resident(const void* score, int score_stride, const int64_t* lm_idx, const int64_t* cur_in,
                              int64_t* cached, int32_t* offsets, int32_t* cnts, int64_t* sel_out, int32_t* dst_slots,
                              int B, int N, int S, int R, int32_t* slot_age, hipStream_t st, const EarlyHooks* hooks = nullptr,
-                             const FusedTop* fused = nullptr, int G = 0);
+                             const FusedTop* fused = nullptr, int G = 0, const KvProj* kv_proj = nullptr);
 bool skv_fused_select_supported(int G, int N, int S);
 int skv_launch_early_init(const EarlyState& es, int B, int G, int n_landmarks, int n_chunks, int E, hipStream_t st);
 int skv_launch_early_map(const EarlyState& es, const int64_t* lm_idx, int B, int N, hipStream_t st);
@@ -389,11 +391,23 @@ int skv_select_state_init(void* state, int blocks, int groups, skv_stream_t stre
     return hipMemsetAsync(state, 0, skv_select_state_bytes(blocks, groups), (hipStream_t)stream) == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
 }
 
-int skv_select_chunks_fused(const void* q, const void* landmarks, const int64_t* landmark_idx, int64_t* cached_pos_ids,
+static int kv_proj_of(KvProj& kp, const skv_kv_proj_t* d) {
+    if (!d->Wqkv || !d->h || !d->norm_weight || !d->cos_sin || !d->pos || !d->row_idx || !d->k_cache || !d->v_cache) return SKV_ERR_ARG;
+    if (d->q_heads < 1 || d->kv_heads < 1 || d->cos_sin_rows < 1 || d->cache_rows < 1) return SKV_ERR_ARG;
+    if (d->placement != SKV_KV_PROJ_IN_SCAN && d->placement != SKV_KV_PROJ_IN_TOPK) return SKV_ERR_ARG;
+    if (d->K != 4096 || d->head_dim != 128 || (d->rope_mode != 1 && d->rope_mode != 2)) return SKV_ERR_UNSUPPORTED;
+    kp = KvProj{(const bf16_t*)d->Wqkv, (const bf16_t*)d->h, (const bf16_t*)d->norm_weight, (const bf16_t*)d->bias, d->eps, 1,
+                QkvEpilogue{(const bf16_t*)d->cos_sin, d->pos, d->row_idx, nullptr, nullptr, (bf16_t*)d->k_cache, (bf16_t*)d->v_cache,
+                            d->cos_sin_stride, d->cache_stride_h, d->q_heads, d->kv_heads, d->cache_rows, d->rope_mode == 2,
+                            d->cos_sin_rows}};
+    return SKV_OK;
+}
+
+static int select_chunks_fused_impl(const void* q, const void* landmarks, const int64_t* landmark_idx, int64_t* cached_pos_ids,
                             int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts, void* workspace, int64_t* selected_out,
                             int blocks, int groups, int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age,
                             float alpha, void* select_state, void* early_state, const void* v_host, long long host_block_stride,
-                            int n_chunks, int early_max, float margin, skv_stream_t stream) {
+                            int n_chunks, int early_max, float margin, const skv_kv_proj_t* kv_proj, skv_stream_t stream) {
     if (!q || !landmarks || !cached_pos_ids || !miss_ids || !cnts || !workspace || !select_state) return SKV_ERR_ARG;
     if (blocks < 1 || n_landmarks < select_sets || select_sets < 1 || resident_sets < select_sets) return SKV_ERR_ARG;
     if (!dst_slots && resident_sets != select_sets) return SKV_ERR_ARG;       // a larger resident set: in-place layout only
@@ -415,11 +429,40 @@ int skv_select_chunks_fused(const void* q, const void* landmarks, const int64_t*
                              n_chunks, early_max);
         hooks = &eh;
     }
-    int rc = skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, st, hooks, &fs);
+    KvProj kp{};
+    const KvProj* in_scan = nullptr;
+    const KvProj* in_topk = nullptr;
+    if (kv_proj) {
+        const int rc = kv_proj_of(kp, kv_proj);
+        if (rc != SKV_OK) return rc;
+        (kv_proj->placement == SKV_KV_PROJ_IN_SCAN ? in_scan : in_topk) = &kp;
+    }
+    int rc = skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, st, hooks, &fs, in_scan);
     if (rc != SKV_OK) return rc;
     return finish(skv_launch_topk_resident(w.score, w.score_stride, landmark_idx, nullptr, cached_pos_ids, miss_ids, cnts,
                                            selected_out, dst_slots, blocks, n_landmarks, select_sets, resident_sets, slot_age, st,
-                                           hooks, &ft, groups));
+                                           hooks, &ft, groups, in_topk));
+}
+
+int skv_select_chunks_fused(const void* q, const void* landmarks, const int64_t* landmark_idx, int64_t* cached_pos_ids,
+                            int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts, void* workspace, int64_t* selected_out,
+                            int blocks, int groups, int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age,
+                            float alpha, void* select_state, void* early_state, const void* v_host, long long host_block_stride,
+                            int n_chunks, int early_max, float margin, skv_stream_t stream) {
+    return select_chunks_fused_impl(q, landmarks, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace, selected_out,
+                                    blocks, groups, n_landmarks, select_sets, resident_sets, slot_age, alpha, select_state,
+                                    early_state, v_host, host_block_stride, n_chunks, early_max, margin, nullptr, stream);
+}
+
+int skv_select_chunks_fused_kv_proj(const void* q, const void* landmarks, const int64_t* landmark_idx, int64_t* cached_pos_ids,
+                                    int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts, void* workspace, int64_t* selected_out,
+                                    int blocks, int groups, int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age,
+                                    float alpha, void* select_state, void* early_state, const void* v_host,
+                                    long long host_block_stride, int n_chunks, int early_max, float margin,
+                                    const skv_kv_proj_t* kv_proj, skv_stream_t stream) {
+    return select_chunks_fused_impl(q, landmarks, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace, selected_out,
+                                    blocks, groups, n_landmarks, select_sets, resident_sets, slot_age, alpha, select_state,
+                                    early_state, v_host, host_block_stride, n_chunks, early_max, margin, kv_proj, stream);
 }
 
 // reference slot order (skv_select_chunks / skv_fetch_kv) with the early fetch

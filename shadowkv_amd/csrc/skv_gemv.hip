@@ -13,6 +13,7 @@
 #include "../../include/shadowkv_hip.h"
 #include "skv_common.h"
 #include "skv_early.h"
+#include "skv_kvproj.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef SKV_GEMV_PRE_R2
@@ -27,19 +28,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // QKV epilogue (QKV == true, W = fused [q; k; v] projection of ONE token, head_dim 128): the wave's 4 rows are two
 // rotation pairs of one head - NeoX: (t, t+64), (t+1, t+65); GLM: (2t', 2t'+1), (2t'+2, 2t'+3) - so lane 0 can rotate
 // q / k at the token's position and write q to q_out and k / v straight into the cache row: the projection, the
-// split, RoPE and update_kv_cache are one launch (same arithmetic as skv_qkv_rope_update_kernel).
-struct QkvEpilogue {
-    const bf16_t* cos_sin;
-    const int64_t* pos;       // [1]
-    const int64_t* row_idx;   // [1]
-    const bf16_t* q_override; // nullable [Hq][128]
-    bf16_t* q_out;            // [Hq][128]
-    bf16_t* k_cache;          // [Hkv][cache_rows][128]
-    bf16_t* v_cache;
-    long long cs_stride, cache_stride_h;
-    int Hq, Hkv, cache_rows, glm, cs_rows;
-};
-
+// split, RoPE and update_kv_cache are one launch (same arithmetic as skv_qkv_rope_update_kernel).  N = Hq * 128: the q rows
+// alone (skv_q_gemv_rope) - the k / v rows are then the role of a later launch (skv_kvproj.h).
 // RMAX (lm_head, N % 16 == 0): the workgroup also leaves the LARGEST of its 16 outputs as an order-preserving 16-bit key in
 // range_max[blockIdx.x] - the sampler (skv_sample.hip) then finds the rows that can hold a top-k logit from N / 16 keys
 // instead of streaming all N logits through one CU.
@@ -107,6 +97,7 @@ __global__ __launch_bounds__(256) void skv_gemv_kernel(const bf16_t* __restrict_
         // its k-step slices (vector 64 u + lane for step u).  One read of x / residual / w_norm per BLOCK.
         __shared__ u32x4 s_xn[512];
         __shared__ float s_ss[4];
+        // (skv_norm_prologue_4096 in skv_kvproj.h restates this block for the k/v role's wider workgroups: keep the two in step)
         const int tid = threadIdx.x;
         u32x4 hx[2];
         float ss = 0.f;
@@ -211,55 +202,7 @@ __global__ __launch_bounds__(256) void skv_gemv_kernel(const bf16_t* __restrict_
         tot[r] = wave_tree_sum(s);
     }
     if (QKV) {
-        if (lane == 0 && unit0 < N) {
-            const int head = unit0 / 128;                       // the wave's R rows belong to one head
-            float o[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) o[r] = bfr(bias ? bfr(tot[r]) + bf2f(bias[rows[r]]) : tot[r]);  // the projection output is bf16
-            const long long row = *qe.row_idx;
-            if (head >= qe.Hq + qe.Hkv) {                       // V: copy into the cache row
-                if (row >= 0 && row < qe.cache_rows) {
-                    bf16_t* dst = qe.v_cache + (long long)(head - qe.Hq - qe.Hkv) * qe.cache_stride_h + row * 128;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) dst[rows[r] - head * 128] = f2bf(o[r]);
-                }
-            } else {
-                const long long pcl = min(max(*qe.pos, 0ll), (long long)qe.cs_rows - 1);   // see skv_dense.hip
-                const bf16_t* cs = qe.cos_sin + pcl * qe.cs_stride;
-                float res[R];
-                int dim[R];
-#pragma unroll
-                for (int p = 0; p < R / 2; ++p) {
-                    const int d1 = rows[2 * p] - head * 128, d2 = rows[2 * p + 1] - head * 128;
-                    dim[2 * p] = d1; dim[2 * p + 1] = d2;
-                    const float x1 = o[2 * p], x2 = o[2 * p + 1];
-                    if (!qe.glm) {                              // pair (t, t+64)
-                        const float c = bf2f(cs[d1]), sn = bf2f(cs[d1 + 64]);
-                        res[2 * p] = bfr(x1 * c) + bfr(-x2 * sn);
-                        res[2 * p + 1] = bfr(x2 * c) + bfr(x1 * sn);
-                    } else if (d1 < 64) {                       // pair (2t, 2t+1), cos[t], sin[32+t]
-                        const float c = bf2f(cs[d1 >> 1]), sn = bf2f(cs[32 + (d1 >> 1)]);
-                        res[2 * p] = bfr(x1 * c) + bfr(-x2 * sn);
-                        res[2 * p + 1] = bfr(x2 * c) + bfr(x1 * sn);
-                    } else {
-                        res[2 * p] = x1; res[2 * p + 1] = x2;   // pass-through dims
-                    }
-                }
-                if (head < qe.Hq) {
-                    bf16_t* dst = qe.q_out + (size_t)head * 128;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        float v = res[r];
-                        if (qe.q_override) v = bf2f(qe.q_override[(size_t)head * 128 + dim[r]]) + v * 0.0f;
-                        dst[dim[r]] = f2bf(v);
-                    }
-                } else if (row >= 0 && row < qe.cache_rows) {
-                    bf16_t* dst = qe.k_cache + (long long)(head - qe.Hq) * qe.cache_stride_h + row * 128;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) dst[dim[r]] = f2bf(res[r]);
-                }
-            }
-        }
+        if (lane == 0 && unit0 < N) skv_qkv_epilogue<R>(qe, bias, rows, tot, unit0);
         return;
     }
     __shared__ uint32_t s_kmax[RMAX ? 4 : 1];
@@ -327,7 +270,7 @@ static int launch_gemv(const void* W, const void* x, const void* bias, void* y, 
                        (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, IARG, (const bf16_t*)residual,        \
                        (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe)
     if (qkv) {
-        if (fuse_silu_mul || N != (qe.Hq + 2 * qe.Hkv) * 128) return SKV_ERR_ARG;
+        if (fuse_silu_mul || (N != (qe.Hq + 2 * qe.Hkv) * 128 && N != qe.Hq * 128)) return SKV_ERR_ARG;
         const int grid = (N + 15) / 16;
         if (norm)   // one rotation pair per wave: 3,072 waves for N = 6144 (two pairs per wave: 200.4 -> 202.3 tok/s)
             hipLaunchKernelGGL((skv_gemv_kernel<2, false, true, true>), dim3((N + 7) / 8), dim3(256), 0, st, (const bf16_t*)W,
@@ -424,4 +367,18 @@ extern "C" int skv_qkv_gemv_rope_update(const void* Wqkv, const void* x, const v
                    (bf16_t*)v_cache, cos_sin_stride, cache_stride_h, q_heads, kv_heads, cache_rows, rope_mode == 2, cos_sin_rows};
     return launch_gemv(Wqkv, x, bias, nullptr, (q_heads + 2 * kv_heads) * 128, K, 0, residual, norm_weight, h_out, eps,
                        norm_weight != nullptr, (hipStream_t)stream, &qe);
+}
+
+// The q rows of skv_qkv_gemv_rope_update alone: same kernel, same waves, a grid that ends behind the last q head.  The k / v
+// rows follow as the role of this layer's selection launch (skv_select_chunks_fused_kv_proj), which reads the h stored here.
+extern "C" int skv_q_gemv_rope(const void* Wqkv, const void* x, const void* residual, const void* norm_weight, float eps,
+                               void* h_out, const void* bias, const void* cos_sin, const int64_t* pos, const void* q_override,
+                               void* q_out, int K, int q_heads, int kv_heads, int head_dim, long long cos_sin_stride,
+                               int cos_sin_rows, int rope_mode, skv_stream_t stream) {
+    if (!cos_sin || !pos || !q_out || !norm_weight || cos_sin_rows < 1 || q_heads < 1 || kv_heads < 1) return SKV_ERR_ARG;
+    if (head_dim != 128 || K != 4096 || (rope_mode != 1 && rope_mode != 2)) return SKV_ERR_UNSUPPORTED;
+    // (no wave of this grid owns a k or v head: the caches are never touched, and the row index every wave's lane 0 loads goes unused)
+    QkvEpilogue qe{(const bf16_t*)cos_sin, pos, pos, (const bf16_t*)q_override, (bf16_t*)q_out, nullptr, nullptr, cos_sin_stride, 0,
+                   q_heads, kv_heads, 0, rope_mode == 2, cos_sin_rows};
+    return launch_gemv(Wqkv, x, bias, nullptr, q_heads * 128, K, 0, residual, norm_weight, h_out, eps, true, (hipStream_t)stream, &qe);
 }

@@ -18,6 +18,7 @@
 #include "skv_select_front.h"
 #include "skv_launch.h"
 #include "skv_early.h"
+#include "skv_kvproj.h"
 
 #define SKV_TILE 256  // columns per partial tile == the reference's ThreadblockShape::kN
 // per-wave phase stamps of the scan (tools/score_probe.hip builds with -DSKV_SCORE_STAMPS; never in the library):
@@ -96,14 +97,25 @@ __device__ __forceinline__ void score_row_group(const f32x2 (&qf)[(GH + 1) / 2][
 // operations as one pass): the later passes' query heads wait in a wave-private LDS copy (no barrier).  Results are
 // bit-identical: every head's total is the same fma chain and the same 16-lane tree whichever other heads travel through
 // the butterfly with it.
-template <int G, int ABL = 0, int WAVES = (G == 8 ? 8 : SKV_SCORE_WAVES), int PD = SKV_SCORE_PD>
+template <int G, int ABL = 0, int WAVES = (G == 8 ? 8 : SKV_SCORE_WAVES), int PD = SKV_SCORE_PD, bool KVP = false>
 __global__ __launch_bounds__(64 * WAVES, SKV_SCORE_MIN_WAVES(G, WAVES)) void skv_score_tile_kernel(
     const bf16_t* __restrict__ q,    // [B][G][128]
     const bf16_t* __restrict__ lm,   // [B][N][128]
     bf16_t* __restrict__ D,          // [B][G][N]
     float* __restrict__ part_max,    // [B][T][G]
     float* __restrict__ part_sum,    // [B][T][G]
-    int N, int T, float alpha, EarlyHooks eh, FusedSel fs) {
+    int N, int T, float alpha, EarlyHooks eh, FusedSel fs, KvProj kp = KvProj{}) {
+    // k/v projection role (skv_kvproj.h; KVP: an instantiation of its own, the plain scan keeps its registers and LDS):
+    // kp.blocks workgroups in grid rows of their own BEHIND the scan's tiles, so the scan's dispatch ramp is not delayed
+    if constexpr (KVP) {
+        const int role_y0 = (int)gridDim.y - (kp.blocks + (int)gridDim.x - 1) / (int)gridDim.x;
+        if ((int)blockIdx.y >= role_y0) {
+            __shared__ __attribute__((aligned(16))) unsigned char s_kvp[SKV_KV_PROJ_LDS_BYTES];
+            const int rb = ((int)blockIdx.y - role_y0) * (int)gridDim.x + (int)blockIdx.x;
+            if (rb < kp.blocks) skv_kv_proj_role<64 * WAVES, false>(kp, rb, threadIdx.x, s_kvp);
+            return;
+        }
+    }
     constexpr int ITERS = 64 / WAVES;               // 4-row wave-instructions per wave
     constexpr int GH = G > 8 ? 4 : G;               // query heads per pass
     constexpr int PASSES = G / GH;
@@ -1129,8 +1141,14 @@ __global__ __launch_bounds__(T2_THREADS) void skv_topk2_kernel(
     // [B][R], the S - cnt misses replace the least recently selected of the R - cnt slots that were not selected now
     // (age = steps since the slot's chunk was last selected, saturating at 62; 63 = empty slot; ties -> lowest slot).
     // R == S: every slot that was not selected is replaced, slot_age is not touched (may be null).
-    int R, int RP /* pow2 >= R */, int32_t* __restrict__ slot_age /* [B][R] */, EarlyHooks eh, FusedTop ft) {
+    int R, int RP /* pow2 >= R */, int32_t* __restrict__ slot_age /* [B][R] */, EarlyHooks eh, FusedTop ft, KvProj kp = KvProj{}) {
     extern __shared__ __attribute__((aligned(16))) int smem[];
+    // k/v projection role (skv_kvproj.h): the last kp.blocks workgroups of the grid; HBM is idle while the selection runs
+    const int sel_grid = (int)gridDim.x - kp.blocks;
+    if ((int)blockIdx.x >= sel_grid) {
+        skv_kv_proj_role<T2_THREADS, true>(kp, (int)blockIdx.x - sel_grid, threadIdx.x, reinterpret_cast<unsigned char*>(smem));
+        return;
+    }
     int* s_hist = smem;                               // [T2_BINS][T2_COPIES]
     int* s_cur = s_hist + T2_BINS * T2_COPIES;        // [SP]   selected landmark slot per output position
     long long* s_id = reinterpret_cast<long long*>(s_cur + SP);   // [SP] its chunk id (-1: not gathered yet)
@@ -1145,9 +1163,9 @@ __global__ __launch_bounds__(T2_THREADS) void skv_topk2_kernel(
     int* s_cand = s_out + 16;                         // [T3_CAND] candidate slots (fused front end)
     float* s_fin = reinterpret_cast<float*>(s_cand + (FG > 0 ? T3_CAND : 0));   // [3 * FG] finals (m, 1 / s) and deltas
     const int tid = threadIdx.x;
-    if (eh.staging != nullptr && (int)blockIdx.x >= (int)gridDim.x / (1 + eh.pull_wgs)) {
+    if (eh.staging != nullptr && (int)blockIdx.x >= sel_grid / (1 + eh.pull_wgs)) {
         // early fetch: the blocks behind the B selection blocks pull (skv_early.h)
-        const int p = (int)blockIdx.x - (int)gridDim.x / (1 + eh.pull_wgs);
+        const int p = (int)blockIdx.x - sel_grid / (1 + eh.pull_wgs);
         if constexpr (FG > 0) skv_early_prep_pull_role<T2_THREADS>(eh, p / eh.pull_wgs, p % eh.pull_wgs, tid, smem);   // no normalise launch: list + pull
         else skv_early_pull_role<T2_THREADS>(eh, p / eh.pull_wgs, p % eh.pull_wgs, tid, smem);
         return;
@@ -1495,25 +1513,38 @@ static inline int next_pow2(int v) {
 
 template <int G>
 static int launch_score_g(const void* q, const void* lm, void* D, float* pmax, float* psum, int B, int N, int T,
-                          float alpha, hipStream_t st, const EarlyHooks& eh, const FusedSel& fs) {
-    hipLaunchKernelGGL((skv_score_tile_kernel<G>), dim3(T, B), dim3(64 * (G == 8 ? 8 : SKV_SCORE_WAVES)), 0, st, (const bf16_t*)q,
-                       (const bf16_t*)lm, (bf16_t*)D, pmax, psum, N, T, alpha, eh, fs);
+                          float alpha, hipStream_t st, const EarlyHooks& eh, const FusedSel& fs, KvProj kp) {
+    constexpr int threads = 64 * (G == 8 ? 8 : SKV_SCORE_WAVES);
+    int role_rows = 0;
+    if (kp.blocks > 0) {             // the role's workgroups: whole grid rows behind the B rows of tiles
+        kp.blocks = skv_kv_proj_blocks(kp.qe.Hkv, threads);
+        role_rows = (kp.blocks + T - 1) / T;
+        if (B + role_rows > 65535) return SKV_ERR_UNSUPPORTED;
+    }
+    if (role_rows > 0)
+        hipLaunchKernelGGL((skv_score_tile_kernel<G, 0, threads / 64, SKV_SCORE_PD, true>), dim3(T, B + role_rows), dim3(threads), 0, st,
+                           (const bf16_t*)q, (const bf16_t*)lm, (bf16_t*)D, pmax, psum, N, T, alpha, eh, fs, kp);
+    else
+        hipLaunchKernelGGL((skv_score_tile_kernel<G>), dim3(T, B), dim3(threads), 0, st, (const bf16_t*)q,
+                           (const bf16_t*)lm, (bf16_t*)D, pmax, psum, N, T, alpha, eh, fs);
     return SKV_OK;
 }
 
 int skv_launch_score(const void* q, const void* lm, void* D, float* pmax, float* psum, int B, int G, int N,
-                     float alpha, hipStream_t st, const EarlyHooks* hooks, const FusedSel* fused) {
+                     float alpha, hipStream_t st, const EarlyHooks* hooks, const FusedSel* fused, const KvProj* kv_proj) {
     const int T = (N + SKV_TILE - 1) / SKV_TILE;
+    KvProj kp{};
+    if (kv_proj) { kp = *kv_proj; kp.blocks = 1; }      // (the launcher of the instantiation sets the count)
     EarlyHooks eh{};
     if (hooks) eh = *hooks;
     FusedSel fs{};
     if (fused) fs = *fused;
     switch (G) {
-        case 1: return launch_score_g<1>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs);
-        case 2: return launch_score_g<2>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs);
-        case 4: return launch_score_g<4>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs);
-        case 8: return launch_score_g<8>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs);
-        case 16: return launch_score_g<16>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs);
+        case 1: return launch_score_g<1>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs, kp);
+        case 2: return launch_score_g<2>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs, kp);
+        case 4: return launch_score_g<4>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs, kp);
+        case 8: return launch_score_g<8>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs, kp);
+        case 16: return launch_score_g<16>(q, lm, D, pmax, psum, B, N, T, alpha, st, eh, fs, kp);
         default: return SKV_ERR_UNSUPPORTED;
     }
 }
@@ -1558,7 +1589,8 @@ int skv_launch_normalize_groupmax(const void* D, const float* pmax, const float*
 template <int SEGV, int FG>
 static int launch_topk2(const void* score, int score_stride, const int64_t* lm_idx, const int64_t* cur_in, int64_t* cached,
                         int32_t* offsets, int32_t* cnts, int64_t* sel_out, int32_t* dst_slots, int B, int N, int S, int H,
-                        int SP, int R, int RP, int32_t* slot_age, hipStream_t st, const EarlyHooks& eh, const FusedTop& ft) {
+                        int SP, int R, int RP, int32_t* slot_age, hipStream_t st, const EarlyHooks& eh, const FusedTop& ft,
+                        const KvProj& kp = KvProj{}) {
     const size_t smem = (size_t)(T2_BINS * T2_COPIES + SP * 5 + RP + H * 2 + 80 + 16 + (FG > 0 ? T3_CAND + 64 : 0)) * sizeof(int);
     static size_t attr_bytes[64] = {};
     if (skv_ensure_max_lds((const void*)skv_topk2_kernel<SEGV, FG>,
@@ -1569,8 +1601,9 @@ static int launch_topk2(const void* score, int score_stride, const int64_t* lm_i
     if (!pull) ek.staging = nullptr;
     ek.pull_wgs = B <= 8 ? SKV_EARLY_PULL_WGS : 1;
     if (pull && FG > 0 && skv_early_prep_lds_bytes(eh.n_chunks) + (EF_MAX_E + 1) * sizeof(int) > smem) return SKV_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((skv_topk2_kernel<SEGV, FG>), dim3(pull ? (1 + ek.pull_wgs) * B : B), dim3(T2_THREADS), smem, st, (const bf16_t*)score, lm_idx, cur_in,
-                       cached, offsets, cnts, sel_out, dst_slots, N, score_stride, S, H, SP, R, RP, slot_age, ek, ft);
+    if (kp.blocks > 0 && smem < SKV_KV_PROJ_LDS_BYTES) return SKV_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((skv_topk2_kernel<SEGV, FG>), dim3((pull ? (1 + ek.pull_wgs) * B : B) + kp.blocks), dim3(T2_THREADS), smem, st, (const bf16_t*)score, lm_idx, cur_in,
+                       cached, offsets, cnts, sel_out, dst_slots, N, score_stride, S, H, SP, R, RP, slot_age, ek, ft, kp);
     return SKV_OK;
 }
 
@@ -1583,7 +1616,13 @@ bool skv_fused_select_supported(int G, int N, int S) {
 int skv_launch_topk_resident(const void* score, int score_stride, const int64_t* lm_idx, const int64_t* cur_in,
                             int64_t* cached, int32_t* offsets, int32_t* cnts, int64_t* sel_out, int32_t* dst_slots,
                             int B, int N, int S, int R, int32_t* slot_age, hipStream_t st, const EarlyHooks* hooks,
-                            const FusedTop* fused, int G) {
+                            const FusedTop* fused, int G, const KvProj* kv_proj) {
+    KvProj kp{};
+    if (kv_proj) {                   // the k/v projection role rides behind the fused selection's workgroups only
+        if (!fused) return SKV_ERR_UNSUPPORTED;
+        kp = *kv_proj;
+        kp.blocks = skv_kv_proj_blocks(kp.qe.Hkv, T2_THREADS);
+    }
     if (S < 1 || S > SKV_SEL_THREADS || R < S || R > T2_THREADS) return SKV_ERR_UNSUPPORTED;
     EarlyHooks eh{};
     if (hooks) eh = *hooks;
@@ -1599,9 +1638,9 @@ int skv_launch_topk_resident(const void* score, int score_stride, const int64_t*
         const int per_thread = (score_stride / 8 + T2_THREADS - 1) / T2_THREADS;
 #define SKV_T3(SV)                                                                                                      \
     return G == 4 ? launch_topk2<SV, 4>(score, score_stride, lm_idx, cur_in, cached, offsets, cnts, sel_out, dst_slots, B, N, S, \
-                                        H, SP, R, RP, slot_age, st, eh, ft)                                             \
+                                        H, SP, R, RP, slot_age, st, eh, ft, kp)                                         \
                   : launch_topk2<SV, 8>(score, score_stride, lm_idx, cur_in, cached, offsets, cnts, sel_out, dst_slots, B, N, S, \
-                                        H, SP, R, RP, slot_age, st, eh, ft)
+                                        H, SP, R, RP, slot_age, st, eh, ft, kp)
         if (per_thread <= 1) { SKV_T3(1); }
         if (per_thread <= 2) { SKV_T3(2); }
         if (per_thread <= 4) { SKV_T3(4); }
@@ -1643,7 +1682,7 @@ int skv_launch_topk_reorder(const void* score, int score_stride, const int64_t* 
                             int64_t* cached, int32_t* offsets, int32_t* cnts, int64_t* sel_out, int32_t* dst_slots,
                             int B, int N, int S, hipStream_t st) {
     return skv_launch_topk_resident(score, score_stride, lm_idx, cur_in, cached, offsets, cnts, sel_out, dst_slots, B, N, S, S,
-                                    nullptr, st, nullptr, nullptr, 0);
+                                    nullptr, st, nullptr, nullptr, 0, nullptr);
 }
 
 #ifdef SKV_TOPK_STAMPS

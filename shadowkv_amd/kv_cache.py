@@ -511,7 +511,14 @@ class ShadowKVCache_CPU:
         self._stage_hits(layer_idx)
         return lv.pos
 
-    def _select_native(self, layer_idx, q, inplace, early_ok=True):
+    def kv_proj_role_supported(self):
+        """Whether this layer state's selection takes the k/v projection role (tensor_op.norm_q_rope): the fused two-launch
+        selection of one sequence."""
+        if not self.fused_select or self._sel_state is None or self.k_landmark is None or self.batch_size != 1:
+            return False
+        return bool(lib().skv_select_fused_supported(self.num_key_value_groups, self.k_landmark.shape[-2], self.select_sets))
+
+    def _select_native(self, layer_idx, q, inplace, early_ok=True, kv_proj=None):
         """The selection launches of one layer (score -> [normalise] -> top-k + diff) on the current stream: the fused two-launch
         form where the kernels take the shape (skv_select_chunks_fused), else the three-launch entries.  inplace: hits keep their
         slots (offsets = miss ids, _dst_slots); else the reference's slot order.  Returns True when an early-fetch list was
@@ -526,15 +533,20 @@ class ShadowKVCache_CPU:
         if inplace and self._dst_slots is None:
             self._dst_slots = torch.zeros_like(self.offsets)
         if self.fused_select and self._sel_state is not None and L.skv_select_fused_supported(G, n, S):
-            check(L.skv_select_chunks_fused(ptr(q), ptr(lm), ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets),
-                                            ptr(self._dst_slots) if inplace else 0, ptr(self.cnts), ptr(self._select_ws), 0,
-                                            self.block_num, G, n, S, R if inplace else S, ptr(lv.age) if inplace else 0, alpha,
-                                            ptr(self._sel_state[layer_idx]), 0 if ea is None else ptr(ea["states"][layer_idx]),
-                                            ptr(vhost), vhost.stride(1), 0 if ea is None else ea["n_chunks"],
-                                            0 if ea is None else ea["E"], 0.0 if ea is None else ea["margin"], st),
-                  "select_chunks_fused")
+            sel_args = (ptr(q), ptr(lm), ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets),
+                        ptr(self._dst_slots) if inplace else 0, ptr(self.cnts), ptr(self._select_ws), 0,
+                        self.block_num, G, n, S, R if inplace else S, ptr(lv.age) if inplace else 0, alpha,
+                        ptr(self._sel_state[layer_idx]), 0 if ea is None else ptr(ea["states"][layer_idx]),
+                        ptr(vhost), vhost.stride(1), 0 if ea is None else ea["n_chunks"],
+                        0 if ea is None else ea["E"], 0.0 if ea is None else ea["margin"])
+            if kv_proj is not None:      # the new token's K / V row is computed by extra workgroups of one of the two launches
+                check(L.skv_select_chunks_fused_kv_proj(*sel_args, ctypes.byref(kv_proj), st), "select_chunks_fused_kv_proj")
+            else:
+                check(L.skv_select_chunks_fused(*sel_args, st), "select_chunks_fused")
             self._near_listed = layer_idx if ea is not None else -1      # (this launch left the layer's near-miss list)
             return ea is not None
+        if kv_proj is not None:
+            raise RuntimeError("the k/v projection role rides in the fused selection launches only (kv_proj_role_supported)")
         if inplace:
             sel_args = (ptr(q), ptr(lm), ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets), ptr(self._dst_slots), ptr(self.cnts),
                         ptr(self._select_ws), 0, 0, self.block_num, G, n, S, R, ptr(lv.age), alpha)
@@ -942,13 +954,15 @@ class ShadowKVCache_CPU:
             pulled += len(early); used += len(early & m); misses += len(m)
         return pulled, used, misses
 
-    def select_fetch_attend_inplace(self, layer_idx, query_states, cos_sin_cache, kv_len=0, kv_len_dev=None):
+    def select_fetch_attend_inplace(self, layer_idx, query_states, cos_sin_cache, kv_len=0, kv_len_dev=None, kv_proj=None):
         """select_fetch_inplace + sparse attention of one layer with the attention over the already-resident rows
         (local, outliers, surviving chunks, generated tokens) running INSIDE the fetch launch, on the CUs the PCIe-bound
         V fetch leaves idle; every miss tile (8 chunks) is attended by the workgroup that rebuilds its K rows and lands
         its V rows, straight from LDS / the landing registers; a small second launch merges the records.
         4 launches + 1 (score, normalize, top-k/diff, rebuild||fetch||attention, merge).  Returns [bs, 1, Hq, D]
-        like tensor_op.sparse_attention_decode; same values up to the order of the f32 sums."""
+        like tensor_op.sparse_attention_decode; same values up to the order of the f32 sums.
+        kv_proj (tensor_op.norm_q_rope): the new token's K / V row is still to be computed - a role of the selection
+        launches does it before the fetch launch attends the generated rows."""
         if query_states.shape[-2] != 1:
             raise ValueError("decode-time selection expects q_len == 1")
         buf_rows = self.k_cache_buffer.shape[-2]
@@ -969,7 +983,7 @@ class ShadowKVCache_CPU:
         ws = tensor_op.attention_workspace(q.device, bs, Hq, SA + self.select_sets // 8)
         kbuf, vbuf = self.k_cache_buffer[layer_idx], self.v_cache_buffer[layer_idx]
         vhost = self.v_cache_cpu[layer_idx]
-        self._select_native(layer_idx, q, inplace=True)
+        self._select_native(layer_idx, q, inplace=True, kv_proj=kv_proj)
         ea = self._early_state()
         U, SV = self.U[layer_idx], self.SV[layer_idx]
         width = cos_sin_cache.shape[-1]

@@ -171,6 +171,12 @@ class DecoderLM:
         # logits as a 16-bit key, the native sampler reads those instead of streaming the row through one CU (same token)
         self.sampler_ranges = True
         self._range_max = None          # int16 [1, vocab / 16 rounded up to 8]
+        # QKV projection split by rows (forward_fused, one sequence, fused selection): only the q rows stream in front of the
+        # landmark scan, the k / v rows are a role of a selection launch (csrc/skv_kvproj.h).  False: the one launch.
+        self.split_kv_proj = True
+        self.kv_proj_placement = tensor_op.KV_PROJ_IN_TOPK     # which selection launch carries the role (KV_PROJ_IN_SCAN: the scan)
+        self.kv_proj_split_launches = 0   # layers forward_fused sent down the split path / through the one launch so far
+        self.kv_proj_fused_launches = 0
         self._last_range_max = None     # the keys of the logits forward_fused returned last (None: not produced)
 
     def weight_bytes(self):
@@ -496,12 +502,27 @@ class DecoderLM:
         for l, layer in enumerate(self.layers):
             kbuf = c.k_cache[l] if full else c.k_cache_buffer[l]
             vbuf = c.v_cache[l] if full else c.v_cache_buffer[l]
-            residual, q = tensor_op.norm_qkv_rope_update(
-                x, residual, layer.input_layernorm_weight, layer.input_layernorm_variance_epsilon, layer.wqkv,
-                layer.bqkv, self.cos_sin_cache, pos, row_idx, kbuf, vbuf, self.num_heads,
-                self.num_key_value_heads, q_override=None if q_table is None else q_table[l])
-            if not full and self.chunk_layout == "inplace" and self.overlap_attention and c.can_overlap_attention():
-                attn = c.select_fetch_attend_inplace(l, q, self.cos_sin_cache, kv_len=kv_len, kv_len_dev=kv_len_dev)
+            overlap = not full and self.chunk_layout == "inplace" and self.overlap_attention and c.can_overlap_attention()
+            # the q rows alone in front of the scan; the k / v rows ride in the selection launches
+            split = bool(self.split_kv_proj and overlap and bs == 1 and c.kv_proj_role_supported()
+                         and tensor_op.kv_proj_split_supported(x, layer.wqkv, kbuf))
+            kv_proj = None
+            if split:
+                residual, q, kv_proj = tensor_op.norm_q_rope(
+                    x, residual, layer.input_layernorm_weight, layer.input_layernorm_variance_epsilon, layer.wqkv,
+                    layer.bqkv, self.cos_sin_cache, pos, row_idx, kbuf, vbuf, self.num_heads,
+                    self.num_key_value_heads, q_override=None if q_table is None else q_table[l],
+                    placement=self.kv_proj_placement)
+                self.kv_proj_split_launches += 1
+            else:
+                residual, q = tensor_op.norm_qkv_rope_update(
+                    x, residual, layer.input_layernorm_weight, layer.input_layernorm_variance_epsilon, layer.wqkv,
+                    layer.bqkv, self.cos_sin_cache, pos, row_idx, kbuf, vbuf, self.num_heads,
+                    self.num_key_value_heads, q_override=None if q_table is None else q_table[l])
+                self.kv_proj_fused_launches += 1
+            if overlap:
+                attn = c.select_fetch_attend_inplace(l, q, self.cos_sin_cache, kv_len=kv_len, kv_len_dev=kv_len_dev,
+                                                     kv_proj=kv_proj)
             else:
                 slot_args = {}
                 if not full and self.chunk_layout == "inplace":

@@ -16,7 +16,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from ._lib import lib, check, ptr, current_stream_handle
+from ._lib import lib, check, ptr, current_stream_handle, KvProjDesc, KV_PROJ_IN_SCAN, KV_PROJ_IN_TOPK  # noqa: F401
 from .kernels import shadowkv
 
 
@@ -171,6 +171,34 @@ def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row
                                          k_cache.shape[2], 1 if cos_sin.shape[-1] == 128 else 2, current_stream_handle()),
           "qkv_gemv_rope_update")
     return h, q
+
+
+def kv_proj_split_supported(x, wqkv, k_cache):
+    """Shapes norm_q_rope + the k/v role take: one token of one sequence, hidden size 4096, head_dim 128."""
+    K = x.shape[-1]
+    return bool(x.is_cuda and x.numel() == K == 4096 and x.is_contiguous() and wqkv.is_contiguous() and k_cache.shape[-1] == 128
+                and k_cache.shape[0] == 1)
+
+
+def norm_q_rope(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_heads, q_override=None,
+                placement=KV_PROJ_IN_TOPK):
+    """(h, q, kv_proj): norm_qkv_rope_update over the q rows of wqkv alone - one native launch; the k / v rows (the new token's
+    cache row) are left to a role of the layer's selection launches: hand kv_proj (a _lib.KvProjDesc) to
+    ShadowKVCache_CPU.select_fetch_attend_inplace(..., kv_proj=).  The descriptor holds raw pointers: h, row_idx, pos and the
+    other arguments must stay alive and unchanged until that call."""
+    if not kv_proj_split_supported(x, wqkv, k_cache):
+        raise ValueError("the q / kv split of the QKV projection takes one token of one sequence, hidden size 4096, head_dim 128")
+    K, D = x.shape[-1], 128
+    q = torch.empty(1, q_heads, 1, D, dtype=x.dtype, device=x.device)
+    h = torch.empty_like(x) if residual is not None else x
+    rope_mode = 1 if cos_sin.shape[-1] == 128 else 2
+    check(lib().skv_q_gemv_rope(ptr(wqkv), ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0,
+                                ptr(bqkv), ptr(cos_sin), ptr(pos), ptr(q_override), ptr(q), K, q_heads, kv_heads, D,
+                                cos_sin.stride(0), cos_sin.shape[0], rope_mode, current_stream_handle()), "q_gemv_rope")
+    desc = KvProjDesc(ptr(wqkv), ptr(h), ptr(norm_w), ptr(bqkv) or None, ptr(cos_sin), ptr(pos), ptr(row_idx), ptr(k_cache),
+                      ptr(v_cache), cos_sin.stride(0), k_cache.stride(1), float(eps), K, q_heads, kv_heads, D, cos_sin.shape[0],
+                      k_cache.shape[2], rope_mode, int(placement))
+    return h, q, desc
 
 
 # ---------------------------------------------------------------------------- RoPE (pure torch, tensor_op.py:127-151)
