@@ -629,6 +629,38 @@ SKV_EXPORT int skv_vs_sparse_attention(const void* q, const void* k, const void*
                             long long k_stride_s, long long v_stride_b, long long v_stride_h, long long v_stride_s,
                             float scale, skv_stream_t stream);
 
+/* ---- part 7: weight-only FP8 (e4m3) decode GEMVs ---------------------------------------------- */
+
+/* The one-token projections above with the weight matrix as OCP e4m3fn bytes W8 [N][K] row-major (torch.float8_e4m3fn; not
+ * MI300's fnuz) and one f32 scale per output row, scale [N]:  W[n][k] = scale[n] * e4m3(W8[n][k]).  x, bias, y and every other
+ * operand stay bf16.  Per output row t = scale[n] * sum_k f32(e4m3(W8[n][k])) * f32(x[k]) (f32 accumulation, one f32 multiply
+ * after the reduction); t then takes exactly the epilogue of the bf16 entry of the same name: bias, fused SiLU * mul, the QKV
+ * split + RoPE + cache push, the sampler's range keys, the near-miss pull role in front of the grid.  h_out of the norm
+ * variants is bit-identical to skv_add_rmsnorm's.
+ * K % 16 == 0 and K >= 1024 (the norm variants: K == 4096), W8 16-byte aligned; anything else: SKV_ERR_UNSUPPORTED.  A null
+ * W8 / scale / x / y or N < 1: SKV_ERR_ARG.  Every argument check runs on the host before any HIP call.  The remaining
+ * arguments are those of skv_gemv_bf16, skv_norm_gemv_bf16, skv_norm_gemv_rangemax_bf16, skv_qkv_gemv_rope_update (all
+ * (q_heads + 2 kv_heads) * 128 rows; there is no q-only form), skv_norm_gemv_near_pull_bf16 and skv_gemv_near_pull_bf16. */
+SKV_EXPORT int skv_gemv_fp8(const void* W8, const void* scale, const void* x, const void* bias, void* y, int N, int K,
+                 int fuse_silu_mul, skv_stream_t stream);
+SKV_EXPORT int skv_norm_gemv_fp8(const void* W8, const void* scale, const void* x, const void* residual, const void* norm_weight,
+                      float eps, void* h_out, const void* bias, void* y, int N, int K, int fuse_silu_mul, skv_stream_t stream);
+SKV_EXPORT int skv_norm_gemv_rangemax_fp8(const void* W8, const void* scale, const void* x, const void* residual,
+                               const void* norm_weight, float eps, void* h_out, const void* bias, void* y, int N, int K,
+                               void* range_max, skv_stream_t stream);
+SKV_EXPORT int skv_qkv_gemv_rope_update_fp8(const void* Wqkv8, const void* scale, const void* x, const void* residual,
+                                 const void* norm_weight, float eps, void* h_out, const void* bias, const void* cos_sin,
+                                 const int64_t* pos, const int64_t* row_idx, const void* q_override, void* q_out, void* k_cache,
+                                 void* v_cache, int K, int q_heads, int kv_heads, int head_dim, long long cos_sin_stride,
+                                 int cos_sin_rows, long long cache_stride_h, int cache_rows, int rope_mode, skv_stream_t stream);
+SKV_EXPORT int skv_norm_gemv_near_pull_fp8(const void* W8, const void* scale, const void* x, const void* residual,
+                                const void* norm_weight, float eps, void* h_out, void* y, int N, int K, void* early_state,
+                                int blocks, int groups, int n_landmarks, int n_chunks, int early_max, const void* v_host,
+                                long long host_block_stride, int pull_parts, int active_lists, skv_stream_t stream);
+SKV_EXPORT int skv_gemv_near_pull_fp8(const void* W8, const void* scale, const void* x, const void* bias, void* y, int N, int K,
+                           void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
+                           const void* v_host, long long host_block_stride, int pull_parts, int list, skv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

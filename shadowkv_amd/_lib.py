@@ -93,6 +93,13 @@ _SIGS = {
     "skv_qkv_gemv_rope_update": (c_int, [c_p] * 4 + [c_f] + [c_p] * 9 + [c_int] * 4 + [c_ll, c_int, c_ll] + [c_int] * 2 + [c_p]),
     "skv_q_gemv_rope": (c_int, [c_p] * 4 + [c_f] + [c_p] * 6 + [c_int] * 4 + [c_ll] + [c_int] * 2 + [c_p]),
     "skv_gemv_bf16": (c_int, [c_p] * 4 + [c_int] * 3 + [c_p]),
+    # weight-only FP8 (e4m3): the bf16 signatures with the f32 row scales behind the weights
+    "skv_gemv_fp8": (c_int, [c_p] * 5 + [c_int] * 3 + [c_p]),
+    "skv_norm_gemv_fp8": (c_int, [c_p] * 5 + [c_f] + [c_p] * 3 + [c_int] * 3 + [c_p]),
+    "skv_norm_gemv_rangemax_fp8": (c_int, [c_p] * 5 + [c_f] + [c_p] * 3 + [c_int] * 2 + [c_p, c_p]),
+    "skv_qkv_gemv_rope_update_fp8": (c_int, [c_p] * 5 + [c_f] + [c_p] * 9 + [c_int] * 4 + [c_ll, c_int, c_ll] + [c_int] * 2 + [c_p]),
+    "skv_norm_gemv_near_pull_fp8": (c_int, [c_p] * 5 + [c_f] + [c_p] * 2 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
+    "skv_gemv_near_pull_fp8": (c_int, [c_p] * 5 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
     "skv_chunk_stats": (c_int, [c_p, c_ll] + [c_int] * 4 + [c_p] * 3),
     "skv_host_alloc": (c_int, [ctypes.POINTER(c_p), c_sz]),
     "skv_host_free": (c_int, [c_p]),

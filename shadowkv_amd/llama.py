@@ -71,6 +71,16 @@ class DecoderLayer:
         self.post_attention_layernorm_weight = torch.ones(h, device=device, dtype=dtype)
         self.input_layernorm_variance_epsilon = cfg.rms_norm_eps
         self.post_attention_layernorm_variance_epsilon = cfg.rms_norm_eps
+        # f32 row scales of the four matrices once DecoderLM.quantize_weights has made them float8_e4m3fn; None: bf16 weights
+        self.wqkv_scale = self.wo_scale = self.gate_up_proj_scale = self.down_proj_scale = None
+
+    MATRICES = ("wqkv", "wo", "gate_up_proj", "down_proj")
+
+    def prefill_weight(self, name):
+        """The matrix as the prefill GEMMs read it: itself (bf16), or a bf16 temporary dequantised from FP8 - one elementwise
+        torch op, freed by the caller's scope."""
+        w, sc = getattr(self, name), getattr(self, name + "_scale")
+        return w if sc is None else tensor_op.dequantize_fp8_rows(w, sc, torch.bfloat16)
 
 
 def build_cos_sin_cache(cfg, max_pos, device, dtype):
@@ -107,11 +117,16 @@ def load_minference_pattern(pattern, num_layers, num_heads):
     return out
 
 
+WEIGHT_DTYPES = ("bf16", "fp8_e4m3")     # "fp8_e4m3": weight-only FP8, per-row f32 scales
+
+
 class DecoderLM:
     def __init__(self, cfg=LLAMA_3_1_8B, batch_size=1, max_length=64 * 1024, device="cuda:0", dtype=torch.bfloat16,
                  attn_mode="shadowkv_cpu", sparse_budget=2048, rank=160, chunk_size=8, random_init=True, seed=1234,
                  num_layers=None, chunk_layout="reference", v_offload=True, overlap_attention=False, max_new_tokens=1024,
-                 resident_sets=None, minference=False, minference_pattern=None):
+                 resident_sets=None, minference=False, minference_pattern=None, weight_dtype="bf16"):
+        if weight_dtype not in WEIGHT_DTYPES:       # (before anything is allocated)
+            raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
         if chunk_layout not in ("reference", "inplace"):
             raise ValueError("chunk_layout must be 'reference' (hits compacted to the front, the reference's slot order) "
                              "or 'inplace' (hits keep their slots, misses take the freed slots)")
@@ -178,12 +193,39 @@ class DecoderLM:
         self.kv_proj_split_launches = 0   # layers forward_fused sent down the split path / through the one launch so far
         self.kv_proj_fused_launches = 0
         self._last_range_max = None     # the keys of the logits forward_fused returned last (None: not produced)
+        self.lm_head_scale = None       # f32 [vocab] once the lm_head is FP8
+        self.weight_dtype = "bf16"
+        if weight_dtype == "fp8_e4m3":  # random bf16 init, then quantised: the same seed gives the bf16 model's weights, quantised
+            self.quantize_weights()
+
+    def quantize_weights(self, pow2_scale=False):
+        """Weight-only FP8 in place: wqkv, wo, gate_up_proj, down_proj of every layer and the lm_head become float8_e4m3fn with
+        one f32 scale per output row (`<name>_scale`, tensor_op.quantize_fp8_rows); embed_tokens, the norm weights and the biases
+        stay bf16.  Idempotent: a model that is already FP8 is left as it is."""
+        if self.weight_dtype == "fp8_e4m3":
+            return self
+        for layer in self.layers:
+            for name in DecoderLayer.MATRICES:
+                w8, sc = tensor_op.quantize_fp8_rows(getattr(layer, name), pow2_scale=pow2_scale)
+                setattr(layer, name, w8)
+                setattr(layer, name + "_scale", sc)
+        self.lm_head, self.lm_head_scale = tensor_op.quantize_fp8_rows(self.lm_head, pow2_scale=pow2_scale)
+        self.weight_dtype = "fp8_e4m3"
+        return self
 
     def weight_bytes(self):
-        n = self.lm_head.numel()   # one embedding row is read per token: not counted
+        """Bytes of the matrices a decode step streams (one embedding row is read per token: not counted); FP8 matrices count
+        their bytes plus 4 per row for the scales."""
+        def nbytes(w, sc):
+            return w.numel() * w.element_size() + (0 if sc is None else sc.numel() * sc.element_size())
+
+        n = nbytes(self.lm_head, self.lm_head_scale)
         for l in self.layers:
-            n += l.wqkv.numel() + l.wo.numel() + l.gate_up_proj.numel() + l.down_proj.numel()
-        return n * 2
+            n += sum(nbytes(getattr(l, name), getattr(l, name + "_scale")) for name in DecoderLayer.MATRICES)
+        return n
+
+    def _lm_head_prefill(self):
+        return self.lm_head if self.lm_head_scale is None else tensor_op.dequantize_fp8_rows(self.lm_head, self.lm_head_scale)
 
     # --------------------------------------------------------------- per-layer pieces (llama.py:283-427)
     def _decode_scratch(self, bs):
@@ -224,10 +266,10 @@ class DecoderLM:
             sc["i"] ^= 1                                        # (a new layer: the other buffer set)
             _, qkv = tensor_op.norm_linear_decode(hidden_states, None, layer.input_layernorm_weight,
                                                   layer.input_layernorm_variance_epsilon, layer.wqkv, layer.bqkv,
-                                                  out=sc["sets"][sc["i"]]["qkv"])
+                                                  out=sc["sets"][sc["i"]]["qkv"], w_scale=layer.wqkv_scale)
         else:
             hs = tensor_op.layer_norm(hidden_states, layer.input_layernorm_variance_epsilon, layer.input_layernorm_weight)
-            qkv = F.linear(hs, layer.wqkv, layer.bqkv)
+            qkv = F.linear(hs, layer.prefill_weight("wqkv"), layer.bqkv)
         q, k, v = qkv.split([layer.q_size, layer.kv_size, layer.kv_size], dim=-1)
         return q, k, v.view(v.shape[0], -1, self.num_key_value_heads, self.head_dim).transpose(1, 2)
 
@@ -290,7 +332,7 @@ class DecoderLM:
         if attn_output.shape[1] == 1 and attn_output.is_cuda:       # one decode token per sequence: native kernels
             sc = self._decode_scratch(attn_output.shape[0])
             cur = sc["sets"][sc["i"]]
-            o = tensor_op.linear_decode(attn_output, layer.wo, out=cur["o"])
+            o = tensor_op.linear_decode(attn_output, layer.wo, out=cur["o"], w_scale=layer.wo_scale)
             # (one sequence on the ShadowKV cache with near_fetch: the launch's first workgroups stage this step's near misses)
             near = None
             if attn_output.shape[0] == 1 and self.attn_mode != "full" and getattr(layer, "layer_idx", None) is not None:
@@ -298,21 +340,24 @@ class DecoderLM:
             residual, act = tensor_op.norm_linear_decode(o, residual, layer.post_attention_layernorm_weight,
                                                          layer.post_attention_layernorm_variance_epsilon,
                                                          layer.gate_up_proj, fuse_silu_mul=True, out=cur["act"], h_out=cur["h"],
-                                                         near_pull=near)
+                                                         near_pull=near, w_scale=layer.gate_up_proj_scale)
             if residual.shape[0] == 1:      # one sequence: the residual rides in the GEMV's bias slot (bf16(W.act) + residual,
                 #                             rounded like the separate add: same bits, one launch less)
                 near1 = None if near is None else self.kv_cache.near_pull_args(layer.layer_idx, 1)
-                return tensor_op.linear_decode(act, layer.down_proj, bias=residual, out=cur["out"], near_pull=near1)
-            return torch.add(residual, tensor_op.linear_decode(act, layer.down_proj, out=cur["down"]), out=cur["out"])
-        hs = residual + F.linear(attn_output, layer.wo)
+                return tensor_op.linear_decode(act, layer.down_proj, bias=residual, out=cur["out"], near_pull=near1,
+                                               w_scale=layer.down_proj_scale)
+            return torch.add(residual, tensor_op.linear_decode(act, layer.down_proj, out=cur["down"], w_scale=layer.down_proj_scale),
+                             out=cur["out"])
+        # (prefill: an FP8 layer's matrices are dequantised to bf16 temporaries as they are reached, each freed after its GEMM)
+        hs = residual + F.linear(attn_output, layer.prefill_weight("wo"))
         residual = hs
         hs = tensor_op.layer_norm(hs, layer.post_attention_layernorm_variance_epsilon,
                                   layer.post_attention_layernorm_weight)
-        hs = F.linear(hs, layer.gate_up_proj)
+        hs = F.linear(hs, layer.prefill_weight("gate_up_proj"))
         d = hs.shape[-1] // 2
         act = torch.empty(hs.shape[:-1] + (d,), dtype=hs.dtype, device=hs.device)
         tensor_op.silu_and_mul(act, hs)
-        return residual + F.linear(act, layer.down_proj)
+        return residual + F.linear(act, layer.prefill_weight("down_proj"))
 
     # --------------------------------------------------------------- decode branch of layer_compute (base.py:315-341)
     @torch.inference_mode()
@@ -393,7 +438,7 @@ class DecoderLM:
         for idx in range(self.num_layers):
             hs = self._prefill_layer(self.layers[idx], idx, hs, pos)
         hs = tensor_op.layer_norm(hs[:, -1:, :], self.norm_variance_epsilon, self.norm_weight)
-        return F.linear(hs, self.lm_head).float()
+        return F.linear(hs, self._lm_head_prefill()).float()
 
     def _check_prompt(self, n, gen_len=0):
         """ValueError, before any layer runs, for a prompt of n tokens (then gen_len decode steps) the model cannot serve."""
@@ -504,7 +549,8 @@ class DecoderLM:
             vbuf = c.v_cache[l] if full else c.v_cache_buffer[l]
             overlap = not full and self.chunk_layout == "inplace" and self.overlap_attention and c.can_overlap_attention()
             # the q rows alone in front of the scan; the k / v rows ride in the selection launches
-            split = bool(self.split_kv_proj and overlap and bs == 1 and c.kv_proj_role_supported()
+            # (FP8 weights: the k/v role reads bf16 rows, so the one QKV launch is taken - kv_proj_split_supported says no)
+            split = bool(self.split_kv_proj and overlap and bs == 1 and layer.wqkv_scale is None and c.kv_proj_role_supported()
                          and tensor_op.kv_proj_split_supported(x, layer.wqkv, kbuf))
             kv_proj = None
             if split:
@@ -518,7 +564,7 @@ class DecoderLM:
                 residual, q = tensor_op.norm_qkv_rope_update(
                     x, residual, layer.input_layernorm_weight, layer.input_layernorm_variance_epsilon, layer.wqkv,
                     layer.bqkv, self.cos_sin_cache, pos, row_idx, kbuf, vbuf, self.num_heads,
-                    self.num_key_value_heads, q_override=None if q_table is None else q_table[l])
+                    self.num_key_value_heads, q_override=None if q_table is None else q_table[l], w_scale=layer.wqkv_scale)
                 self.kv_proj_fused_launches += 1
             if overlap:
                 attn = c.select_fetch_attend_inplace(l, q, self.cos_sin_cache, kv_len=kv_len, kv_len_dev=kv_len_dev,
@@ -536,14 +582,16 @@ class DecoderLM:
                         c.fetch_kv_follows = False
                     c.fetch_kv(l, ids, self.cos_sin_cache)
                 attn = tensor_op.sparse_attention_decode(q, kbuf, vbuf, kv_len=kv_len, kv_len_dev=kv_len_dev, **slot_args)
-            o = tensor_op.linear_decode(attn.reshape(bs, 1, self.hidden_size), layer.wo)
+            o = tensor_op.linear_decode(attn.reshape(bs, 1, self.hidden_size), layer.wo, w_scale=layer.wo_scale)
             # residual add + RMSNorm ride in the gate/up GEMV's block-cooperative prologue (one launch when bs == 1
             # and hidden == 4096, bit-identical to add_rmsnorm + GEMV; otherwise norm_linear_decode splits it)
             residual, act = tensor_op.norm_linear_decode(o, residual, layer.post_attention_layernorm_weight,
                                                          layer.post_attention_layernorm_variance_epsilon,
                                                          layer.gate_up_proj, fuse_silu_mul=True,
-                                                         near_pull=None if full or bs != 1 else c.near_pull_args(l))
-            x = tensor_op.linear_decode(act, layer.down_proj, near_pull=None if full or bs != 1 else c.near_pull_args(l, 1))
+                                                         near_pull=None if full or bs != 1 else c.near_pull_args(l),
+                                                         w_scale=layer.gate_up_proj_scale)
+            x = tensor_op.linear_decode(act, layer.down_proj, near_pull=None if full or bs != 1 else c.near_pull_args(l, 1),
+                                        w_scale=layer.down_proj_scale)
         V = self.lm_head.shape[0]
         rm = None
         if self.sampler_ranges and not as_float and x.is_cuda and tensor_op.range_max_supported(x.numel(), x.shape[-1], V):
@@ -552,7 +600,7 @@ class DecoderLM:
             rm = self._range_max
         self._last_range_max = rm
         _, logits = tensor_op.norm_linear_decode(x, residual, self.norm_weight, self.norm_variance_epsilon, self.lm_head,
-                                                 range_max=rm)
+                                                 range_max=rm, w_scale=self.lm_head_scale)
         return logits.float() if as_float else logits        # (the native sampler reads the bf16 row as it is)
 
     def get_ctx(self, input_ids):
@@ -566,10 +614,11 @@ class DecoderLM:
         for idx in range(self.num_layers):
             hs = self.layer_compute(self.layers[idx], idx, hs, position_ids)
         if hs.shape[1] == 1 and hs.is_cuda:
-            _, logits = tensor_op.norm_linear_decode(hs, None, self.norm_weight, self.norm_variance_epsilon, self.lm_head)
+            _, logits = tensor_op.norm_linear_decode(hs, None, self.norm_weight, self.norm_variance_epsilon, self.lm_head,
+                                                     w_scale=self.lm_head_scale)
             return logits.float() if as_float else logits    # (bf16: tensor_op.sample_token then samples in one launch)
         hs = tensor_op.layer_norm(hs, self.norm_variance_epsilon, self.norm_weight)
-        return F.linear(hs, self.lm_head).float()
+        return F.linear(hs, self._lm_head_prefill()).float()
 
     @torch.inference_mode()
     def decode_step(self, next_token, temperature=0.6, top_p=0.9, top_k=50, q_table=None, fused=True):

@@ -36,17 +36,75 @@ def silu_and_mul(out, x):
     return out
 
 
+# ---------------------------------------------------------------------------- weight-only FP8
+FP8_MAX = 448.0       # largest finite e4m3fn value
+
+
+def quantize_fp8_rows(w, pow2_scale=False):
+    """(w8, scale): w [N, K] -> e4m3fn bytes [N, K] (torch.float8_e4m3fn, the OCP encoding) and one f32 scale per row with
+    w[n][k] ~ scale[n] * e4m3(w8[n][k]).  scale[n] = max|w[n]| / 448 (pow2_scale: rounded UP to a power of two, so that
+    scale * e4m3 is a bf16 number); an all-zero row gets scale 1.  The quotient is clamped to +-448 before the cast - torch's
+    cast does not saturate (500 -> the NaN byte 0x7F) - so no 0x7F / 0xFF byte is ever produced.  Host-side torch ops only."""
+    if w.dim() != 2:
+        raise ValueError("quantize_fp8_rows takes a [N, K] matrix")
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    scale = amax / FP8_MAX
+    if pow2_scale:
+        m, e = torch.frexp(scale.clamp_min(2.0 ** -126))        # scale = m * 2^e, m in [0.5, 1): exact, unlike log2
+        scale = torch.ldexp(torch.ones_like(scale), torch.where(m == 0.5, e - 1, e))
+    # (a row whose largest magnitude is below the smallest normal f32 * 448 is quantised against scale 2^-126: still finite)
+    scale = torch.where(amax > 0, scale.clamp_min(2.0 ** -126), torch.ones_like(scale))
+    w8 = (wf / scale.unsqueeze(1)).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return w8.contiguous(), scale.contiguous()
+
+
+def dequantize_fp8_rows(w8, scale, dtype=torch.bfloat16):
+    """scale[n] * e4m3(w8[n][k]) as `dtype` (one f32 multiply, one rounding): what prefill, the FP8 fallbacks and the tests use."""
+    return (w8.float() * scale.float().unsqueeze(1)).to(dtype)
+
+
+def _fp8_check(w, w_scale):
+    if w.dtype != torch.float8_e4m3fn:
+        raise ValueError("w_scale goes with float8_e4m3fn weights")
+    if w_scale.dtype != torch.float32 or w_scale.numel() != w.shape[0] or not w_scale.is_contiguous():
+        raise ValueError("w_scale must be a contiguous f32 vector with one entry per weight row")
+
+
+def _fp8_native(x, w, rows):
+    """Shapes the FP8 GEMV kernels take: one token row, K % 16 == 0, K >= 1024, contiguous operands."""
+    K = x.shape[-1]
+    return rows == 1 and K % 16 == 0 and K >= 1024 and x.is_contiguous() and w.is_contiguous()
+
+
+fp8_native_calls = 0      # native FP8 launches / dequantising fallbacks taken so far (diagnostics; the tests read them)
+fp8_fallback_calls = 0
+
+
+def _fp8_linear_fallback(x, w, w_scale, bias, fuse_silu_mul):
+    """CORRECT AND SLOW: the weights are dequantised to a bf16 temporary on every call, then F.linear (more than one token row,
+    K < 1024, non-contiguous operands)."""
+    global fp8_fallback_calls
+    fp8_fallback_calls += 1
+    out = F.linear(x, dequantize_fp8_rows(w, w_scale, x.dtype), bias)
+    return silu_and_mul_fused(out) if fuse_silu_mul else out
+
+
 MAX_GEMV_ROWS = 32   # token rows served by the native kernels (1: GEMV, 2..32: small-M MFMA kernel); more -> F.linear
 
 
-def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None):
+def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None, w_scale=None):
     """F.linear for decode-time activations (x [..., K] with a handful of token rows): one token -> the native GEMV,
     2..MAX_GEMV_ROWS tokens -> the native small-M MFMA kernel (weights stream once); falls back to F.linear for more
     rows or shapes the kernels are not built for.  fuse_silu_mul: w = [gate; up] -> silu(gate.x) * (up.x).
     near_pull (the down projection of a ShadowKV layer, one token, N <= 8192; ShadowKVCache_CPU.near_pull_args(layer, 1)): the
-    launch's first workgroups stage the second near-miss list of this step's selection (skv_gemv_near_pull_bf16); same y."""
+    launch's first workgroups stage the second near-miss list of this step's selection (skv_gemv_near_pull_bf16); same y.
+    w_scale (f32 [N]): w holds float8_e4m3fn bytes (quantize_fp8_rows) - one token takes the native FP8 GEMV; more token rows,
+    K < 1024 or non-contiguous operands fall back to F.linear over the dequantised weights (correct, slow)."""
     K = x.shape[-1]
     rows = x.numel() // K
+    if w_scale is not None:
+        return _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows)
     if near_pull is not None:
         N = w.shape[0]
         if rows != 1 or fuse_silu_mul or N > 8192 or K % 32 or K < 512 or not x.is_contiguous() or not w.is_contiguous():
@@ -70,22 +128,48 @@ def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None
     return y
 
 
+def _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows):
+    global fp8_native_calls
+    _fp8_check(w, w_scale)
+    N = w.shape[0]
+    if near_pull is not None:
+        if not _fp8_native(x, w, rows) or fuse_silu_mul or N > 8192:
+            raise ValueError("near_pull rides in a one-token GEMV launch with at most 8,192 output rows")
+        y = out if out is not None else torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
+        check(lib().skv_gemv_near_pull_fp8(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, *near_pull,
+                                           current_stream_handle()), "gemv_near_pull_fp8")
+        fp8_native_calls += 1
+        return y
+    if not _fp8_native(x, w, rows):
+        y = _fp8_linear_fallback(x, w, w_scale, bias, fuse_silu_mul)
+        return y if out is None else out.copy_(y)
+    y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
+    check(lib().skv_gemv_fp8(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0,
+                             current_stream_handle()), "gemv_fp8")
+    fp8_native_calls += 1
+    return y
+
+
 def range_max_supported(x_numel, K, N):
     """Whether norm_linear_decode(..., range_max=) takes the one-launch path that fills the sampler's range keys."""
     return x_numel == K == 4096 and N % 16 == 0 and N // 16 <= 16384
 
 
 def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=False, out=None, h_out=None, range_max=None,
-                       near_pull=None):
+                       near_pull=None, w_scale=None):
     """(h, y): h = x + residual (residual None -> h = x), y = linear(RMSNorm(h) * norm_w) for one token, one
     native launch when the hidden size is 4096; otherwise add_rmsnorm + linear_decode.  out / h_out: caller-owned
     result buffers (the eager decode paths reuse theirs instead of allocating per call).
     range_max (lm_head only; int16 [>= N // 16], 16-B aligned; range_max_supported(...) must hold): the launch also leaves the
     largest of every 16 outputs as the sampler's 16-bit key (sample_token_native(..., range_max=)).
     near_pull (gate/up launch of a ShadowKV layer only; ShadowKVCache_CPU.near_pull_args(layer)): the launch's first workgroups
-    stage the near misses of this step's selection ahead of the next step (skv_norm_gemv_near_pull_bf16); same y."""
+    stage the near misses of this step's selection ahead of the next step (skv_norm_gemv_near_pull_bf16); same y.
+    w_scale (f32 [N]): w holds float8_e4m3fn bytes - the same one-launch paths with the FP8 kernels (same h, bit for bit);
+    other shapes: add_rmsnorm + linear_decode(..., w_scale=)."""
     K = x.shape[-1]
     N = w.shape[0]
+    if w_scale is not None:
+        return _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull)
     if near_pull is not None:
         if not fuse_silu_mul or bias is not None or range_max is not None or x.numel() != K or K != 4096 \
                 or not x.is_contiguous() or not w.is_contiguous():
@@ -113,6 +197,33 @@ def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=Fal
     check(lib().skv_norm_gemv_bf16(ptr(w), ptr(x), ptr(residual), ptr(norm_w), float(eps),
                                    ptr(h) if residual is not None else 0, ptr(bias), ptr(y), N, K,
                                    1 if fuse_silu_mul else 0, current_stream_handle()), "norm_gemv")
+    return h, y
+
+
+def _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull):
+    global fp8_native_calls
+    _fp8_check(w, w_scale)
+    K, N = x.shape[-1], w.shape[0]
+    one_launch = x.numel() == K == 4096 and x.is_contiguous() and w.is_contiguous()
+    if near_pull is not None and (not one_launch or not fuse_silu_mul or bias is not None or range_max is not None):
+        raise ValueError("near_pull rides in the one-token gate/up launch (hidden size 4096, fused SiLU * mul, no bias)")
+    if range_max is not None and (not one_launch or fuse_silu_mul or not range_max_supported(x.numel(), K, N)):
+        raise ValueError("range_max: one token, hidden size 4096, N % 16 == 0, N <= 262,144, no fused SiLU")
+    if not one_launch:
+        h, hs = add_rmsnorm(x, residual, norm_w, eps)
+        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale)
+    y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
+    h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
+    head = (ptr(w), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0)
+    if near_pull is not None:
+        check(lib().skv_norm_gemv_near_pull_fp8(*head, ptr(y), N, K, *near_pull, current_stream_handle()), "norm_gemv_near_pull_fp8")
+    elif range_max is not None:
+        check(lib().skv_norm_gemv_rangemax_fp8(*head, ptr(bias), ptr(y), N, K, ptr(range_max), current_stream_handle()),
+              "norm_gemv_rangemax_fp8")
+    else:
+        check(lib().skv_norm_gemv_fp8(*head, ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0, current_stream_handle()),
+              "norm_gemv_fp8")
+    fp8_native_calls += 1
     return h, y
 
 
@@ -153,17 +264,30 @@ def qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_he
 
 
 def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads,
-                         kv_heads, q_override=None):
+                         kv_heads, q_override=None, w_scale=None):
     """(h, q) for ONE token of ONE sequence: h = x + residual, q = RoPE(split(linear(RMSNorm(h)))) [1, Hq, 1, D];
     rotated k and v are pushed into row row_idx of k_cache / v_cache [1, Hkv, rows, D].  One native launch when the
-    hidden size is 4096 and bs == 1; otherwise norm_linear_decode + qkv_rope_update."""
+    hidden size is 4096 and bs == 1; otherwise norm_linear_decode + qkv_rope_update.
+    w_scale (f32 [rows of wqkv]): wqkv holds float8_e4m3fn bytes - the same two paths with the FP8 kernels."""
+    global fp8_native_calls
     K = x.shape[-1]
     D = k_cache.shape[-1]
+    if w_scale is not None:
+        _fp8_check(wqkv, w_scale)
     if x.numel() != K or K != 4096 or not x.is_contiguous() or not wqkv.is_contiguous() or D != 128:
-        h, qkv = norm_linear_decode(x, residual, norm_w, eps, wqkv, bqkv)
+        h, qkv = norm_linear_decode(x, residual, norm_w, eps, wqkv, bqkv, w_scale=w_scale)
         return h, qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_heads, q_override)
     q = torch.empty(1, q_heads, 1, D, dtype=x.dtype, device=x.device)
     h = torch.empty_like(x) if residual is not None else x
+    if w_scale is not None:
+        check(lib().skv_qkv_gemv_rope_update_fp8(ptr(wqkv), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps),
+                                                 ptr(h) if residual is not None else 0, ptr(bqkv), ptr(cos_sin), ptr(pos),
+                                                 ptr(row_idx), ptr(q_override), ptr(q), ptr(k_cache), ptr(v_cache), K, q_heads,
+                                                 kv_heads, D, cos_sin.stride(0), cos_sin.shape[0], k_cache.stride(1),
+                                                 k_cache.shape[2], 1 if cos_sin.shape[-1] == 128 else 2, current_stream_handle()),
+              "qkv_gemv_rope_update_fp8")
+        fp8_native_calls += 1
+        return h, q
     check(lib().skv_qkv_gemv_rope_update(ptr(wqkv), ptr(x), ptr(residual), ptr(norm_w), float(eps),
                                          ptr(h) if residual is not None else 0, ptr(bqkv), ptr(cos_sin), ptr(pos),
                                          ptr(row_idx), ptr(q_override), ptr(q), ptr(k_cache), ptr(v_cache), K, q_heads,
@@ -174,9 +298,10 @@ def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row
 
 
 def kv_proj_split_supported(x, wqkv, k_cache):
-    """Shapes norm_q_rope + the k/v role take: one token of one sequence, hidden size 4096, head_dim 128."""
+    """Shapes norm_q_rope + the k/v role take: one token of one sequence, hidden size 4096, head_dim 128, bf16 weights (the
+    k/v role reads bf16 rows: FP8 models use the one QKV launch)."""
     K = x.shape[-1]
-    return bool(x.is_cuda and x.numel() == K == 4096 and x.is_contiguous() and wqkv.is_contiguous() and k_cache.shape[-1] == 128
+    return bool(wqkv.dtype == torch.bfloat16 and x.is_cuda and x.numel() == K == 4096 and x.is_contiguous() and wqkv.is_contiguous() and k_cache.shape[-1] == 128
                 and k_cache.shape[0] == 1)
 
 
@@ -186,6 +311,8 @@ def norm_q_rope(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row_idx, k_c
     cache row) are left to a role of the layer's selection launches: hand kv_proj (a _lib.KvProjDesc) to
     ShadowKVCache_CPU.select_fetch_attend_inplace(..., kv_proj=).  The descriptor holds raw pointers: h, row_idx, pos and the
     other arguments must stay alive and unchanged until that call."""
+    if wqkv.dtype == torch.float8_e4m3fn:
+        raise ValueError("the q / kv split of the QKV projection reads bf16 weight rows: FP8 weights take norm_qkv_rope_update")
     if not kv_proj_split_supported(x, wqkv, k_cache):
         raise ValueError("the q / kv split of the QKV projection takes one token of one sequence, hidden size 4096, head_dim 128")
     K, D = x.shape[-1], 128

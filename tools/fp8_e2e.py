@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""tokens/s of the headline configuration (Llama-3.1-8B shapes, 122 K synthetic context, budget 2048, hipGraph, in-place
+layout with overlap_attention, bs 1) with bf16 weights and with weight-only FP8 weights, on one box in one process: the bf16
+model is built and timed, then quantised in place (DecoderLM.quantize_weights) and timed again over the SAME context and
+query walk.  usage: tools/fp8_e2e.py [--steps K] [--warmup W] [--layers L] [--out FILE]   (FILE is appended to)"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+from shadowkv_amd import llama  # noqa: E402
+
+
+def run(model, ctx, steps, warmup, seed=4242):
+    c = model.kv_cache
+    c.kv_offset, c.gen_offset = ctx, 0                  # back to the state right after the prefill
+    table = llama.make_walk_table(model, warmup + steps + 6, step=0.3, seed=seed)
+    dec = llama.GraphDecoder(model, temperature=0.6, walk_table=table, ring_slack=True)
+    dec.token.copy_(torch.randint(0, model.vocab_size, (1, 1), device=model.device, generator=torch.Generator(device=model.device).manual_seed(1)))
+    dec.capture()
+    for _ in range(warmup):
+        dec.step()[:, -1].tolist()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        dec.step()[:, -1].tolist()                      # per-step host sync, as the benchmark
+    torch.cuda.synchronize()
+    return steps / (time.perf_counter() - t0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--layers", type=int, default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    ctx, dev = 122 * 1024, "cuda:0"
+    model = llama.DecoderLM(cfg=llama.LLAMA_3_1_8B, batch_size=1, max_length=ctx, device=dev, sparse_budget=2048, rank=160,
+                            chunk_size=8, num_layers=a.layers, chunk_layout="inplace", overlap_attention=True,
+                            max_new_tokens=max(1024, 8 * (a.warmup + a.steps) + 256))
+    llama.build_synthetic_context(model, ctx, seed=4321)
+    model.kv_cache.enable_early_fetch(near=True)        # the headline's default for G <= 4
+    res = {}
+    res["bf16"] = (run(model, ctx, a.steps, a.warmup), model.weight_bytes(), model.kv_proj_split_launches > 0)
+    model.quantize_weights()
+    torch.cuda.empty_cache()
+    res["fp8_e4m3"] = (run(model, ctx, a.steps, a.warmup), model.weight_bytes(), False)
+    lines = [f"# tools/fp8_e2e.py on {torch.cuda.get_device_name(0)}: 122 K synthetic context, budget 2048, hipGraph, in-place + "
+             f"overlap_attention, bs 1, {model.num_layers} layers, {a.steps} steps after {a.warmup} warm-up steps"]
+    for k, (tps, nbytes, split) in res.items():
+        lines.append(f"weight_dtype {k:<9} {tps:8.2f} tokens/s  {1e6 / tps / model.num_layers:7.2f} us/layer  weights {nbytes / 1e9:6.2f} GB"
+                     f"  qkv {'split (q launch + k/v role)' if split else 'one launch'}")
+    lines.append(f"fp8 : bf16 tokens/s ratio {res['fp8_e4m3'][0] / res['bf16'][0]:.3f}")
+    print("\n".join(lines))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
