@@ -661,6 +661,17 @@ SKV_EXPORT int skv_gemv_near_pull_fp8(const void* W8, const void* scale, const v
                            void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
                            const void* v_host, long long host_block_stride, int pull_parts, int list, skv_stream_t stream);
 
+/* The FP8 sibling of skv_linear_rows_bf16: 2..32 token rows (1 works too) against the same W8 / scale
+ * pair, the weights streamed once.  X [M][K] bf16, Y [M][N] bf16 ([M][N/2] with fuse_silu_mul, W8 = [gate; up], each row its own
+ * scale), bias bf16 [N] or null.  Per output t = scale[n] * sum_k f32(e4m3(W8[n][k])) * f32(X[m][k]): f32 accumulation
+ * (v_mfma_f32_16x16x32_bf16 on the exactly converted weights; no FP8 activation, no FP8 MFMA), the split-K partials summed in wave
+ * order, ONE f32 multiply by the scale; then the epilogue of skv_linear_rows_bf16: bf16(t), bf16(bf16r(t) + bias[n]), or
+ * bf16(bf16r(silu(bf16r(t_g))) * bf16r(t_u)).
+ * Checked on the host before any HIP call: a null W8 / scale / X / Y, M < 1, N < 1, fuse_silu_mul with an odd N or a bias:
+ * SKV_ERR_ARG; M > 32, K % 64 != 0 or K < 64: SKV_ERR_UNSUPPORTED.  W8 and X 16-byte aligned. */
+SKV_EXPORT int skv_linear_rows_fp8(const void* W8, const void* scale, const void* X, const void* bias, void* Y, int M, int N, int K,
+                        int fuse_silu_mul, skv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

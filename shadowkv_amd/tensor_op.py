@@ -77,13 +77,26 @@ def _fp8_native(x, w, rows):
     return rows == 1 and K % 16 == 0 and K >= 1024 and x.is_contiguous() and w.is_contiguous()
 
 
+def _fp8_native_rows(x, w, rows):
+    """Shapes skv_linear_rows_fp8 takes: 2..MAX_GEMV_ROWS token rows, K % 64 == 0, contiguous operands."""
+    return 2 <= rows <= MAX_GEMV_ROWS and x.shape[-1] % 64 == 0 and x.is_contiguous() and w.is_contiguous()
+
+
+FP8_ROWS_MODES = ("fallback", "native")    # what 2..MAX_GEMV_ROWS token rows against FP8 weights take (linear_decode)
+
+
+def _fp8_rows_check(fp8_rows):
+    if fp8_rows not in FP8_ROWS_MODES:
+        raise ValueError(f"fp8_rows must be one of {FP8_ROWS_MODES}, got {fp8_rows!r}")
+
+
 fp8_native_calls = 0      # native FP8 launches / dequantising fallbacks taken so far (diagnostics; the tests read them)
 fp8_fallback_calls = 0
 
 
 def _fp8_linear_fallback(x, w, w_scale, bias, fuse_silu_mul):
-    """CORRECT AND SLOW: the weights are dequantised to a bf16 temporary on every call, then F.linear (more than one token row,
-    K < 1024, non-contiguous operands)."""
+    """CORRECT AND SLOW: the weights are dequantised to a bf16 temporary on every call, then F.linear (more than one token row
+    unless fp8_rows="native" serves them, K < 1024 at one row, non-contiguous operands)."""
     global fp8_fallback_calls
     fp8_fallback_calls += 1
     out = F.linear(x, dequantize_fp8_rows(w, w_scale, x.dtype), bias)
@@ -93,18 +106,22 @@ def _fp8_linear_fallback(x, w, w_scale, bias, fuse_silu_mul):
 MAX_GEMV_ROWS = 32   # token rows served by the native kernels (1: GEMV, 2..32: small-M MFMA kernel); more -> F.linear
 
 
-def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None, w_scale=None):
+def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None, w_scale=None, fp8_rows="fallback"):
     """F.linear for decode-time activations (x [..., K] with a handful of token rows): one token -> the native GEMV,
     2..MAX_GEMV_ROWS tokens -> the native small-M MFMA kernel (weights stream once); falls back to F.linear for more
     rows or shapes the kernels are not built for.  fuse_silu_mul: w = [gate; up] -> silu(gate.x) * (up.x).
     near_pull (the down projection of a ShadowKV layer, one token, N <= 8192; ShadowKVCache_CPU.near_pull_args(layer, 1)): the
     launch's first workgroups stage the second near-miss list of this step's selection (skv_gemv_near_pull_bf16); same y.
     w_scale (f32 [N]): w holds float8_e4m3fn bytes (quantize_fp8_rows) - one token takes the native FP8 GEMV; more token rows,
-    K < 1024 or non-contiguous operands fall back to F.linear over the dequantised weights (correct, slow)."""
+    K < 1024 or non-contiguous operands fall back to F.linear over the dequantised weights (correct, slow).
+    fp8_rows ("fallback" | "native"; read with w_scale only): "native" sends 2..MAX_GEMV_ROWS contiguous token rows with
+    K % 64 == 0 through skv_linear_rows_fp8 - the FP8 bytes stream once, nothing is dequantised; every
+    other multi-row shape still falls back.  One token row, near_pull and the default are unchanged."""
+    _fp8_rows_check(fp8_rows)
     K = x.shape[-1]
     rows = x.numel() // K
     if w_scale is not None:
-        return _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows)
+        return _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, fp8_rows)
     if near_pull is not None:
         N = w.shape[0]
         if rows != 1 or fuse_silu_mul or N > 8192 or K % 32 or K < 512 or not x.is_contiguous() or not w.is_contiguous():
@@ -128,7 +145,7 @@ def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None
     return y
 
 
-def _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows):
+def _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, fp8_rows="fallback"):
     global fp8_native_calls
     _fp8_check(w, w_scale)
     N = w.shape[0]
@@ -138,6 +155,12 @@ def _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, ro
         y = out if out is not None else torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
         check(lib().skv_gemv_near_pull_fp8(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, *near_pull,
                                            current_stream_handle()), "gemv_near_pull_fp8")
+        fp8_native_calls += 1
+        return y
+    if fp8_rows == "native" and _fp8_native_rows(x, w, rows):
+        y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
+        check(lib().skv_linear_rows_fp8(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), rows, N, K, 1 if fuse_silu_mul else 0,
+                                        current_stream_handle()), "linear_rows_fp8")
         fp8_native_calls += 1
         return y
     if not _fp8_native(x, w, rows):
@@ -156,7 +179,7 @@ def range_max_supported(x_numel, K, N):
 
 
 def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=False, out=None, h_out=None, range_max=None,
-                       near_pull=None, w_scale=None):
+                       near_pull=None, w_scale=None, fp8_rows="fallback"):
     """(h, y): h = x + residual (residual None -> h = x), y = linear(RMSNorm(h) * norm_w) for one token, one
     native launch when the hidden size is 4096; otherwise add_rmsnorm + linear_decode.  out / h_out: caller-owned
     result buffers (the eager decode paths reuse theirs instead of allocating per call).
@@ -165,11 +188,13 @@ def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=Fal
     near_pull (gate/up launch of a ShadowKV layer only; ShadowKVCache_CPU.near_pull_args(layer)): the launch's first workgroups
     stage the near misses of this step's selection ahead of the next step (skv_norm_gemv_near_pull_bf16); same y.
     w_scale (f32 [N]): w holds float8_e4m3fn bytes - the same one-launch paths with the FP8 kernels (same h, bit for bit);
-    other shapes: add_rmsnorm + linear_decode(..., w_scale=)."""
+    other shapes: add_rmsnorm + linear_decode(..., w_scale=, fp8_rows=) - fp8_rows as in linear_decode."""
+    _fp8_rows_check(fp8_rows)
     K = x.shape[-1]
     N = w.shape[0]
     if w_scale is not None:
-        return _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull)
+        return _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
+                                       fp8_rows)
     if near_pull is not None:
         if not fuse_silu_mul or bias is not None or range_max is not None or x.numel() != K or K != 4096 \
                 or not x.is_contiguous() or not w.is_contiguous():
@@ -200,7 +225,8 @@ def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=Fal
     return h, y
 
 
-def _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull):
+def _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
+                            fp8_rows="fallback"):
     global fp8_native_calls
     _fp8_check(w, w_scale)
     K, N = x.shape[-1], w.shape[0]
@@ -211,7 +237,7 @@ def _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_sil
         raise ValueError("range_max: one token, hidden size 4096, N % 16 == 0, N <= 262,144, no fused SiLU")
     if not one_launch:
         h, hs = add_rmsnorm(x, residual, norm_w, eps)
-        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale)
+        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale, fp8_rows=fp8_rows)
     y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
     h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
     head = (ptr(w), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0)
@@ -264,18 +290,20 @@ def qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_he
 
 
 def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads,
-                         kv_heads, q_override=None, w_scale=None):
+                         kv_heads, q_override=None, w_scale=None, fp8_rows="fallback"):
     """(h, q) for ONE token of ONE sequence: h = x + residual, q = RoPE(split(linear(RMSNorm(h)))) [1, Hq, 1, D];
     rotated k and v are pushed into row row_idx of k_cache / v_cache [1, Hkv, rows, D].  One native launch when the
     hidden size is 4096 and bs == 1; otherwise norm_linear_decode + qkv_rope_update.
-    w_scale (f32 [rows of wqkv]): wqkv holds float8_e4m3fn bytes - the same two paths with the FP8 kernels."""
+    w_scale (f32 [rows of wqkv]): wqkv holds float8_e4m3fn bytes - the same two paths with the FP8 kernels; fp8_rows as in
+    linear_decode (the multi-row path's projection)."""
     global fp8_native_calls
+    _fp8_rows_check(fp8_rows)
     K = x.shape[-1]
     D = k_cache.shape[-1]
     if w_scale is not None:
         _fp8_check(wqkv, w_scale)
     if x.numel() != K or K != 4096 or not x.is_contiguous() or not wqkv.is_contiguous() or D != 128:
-        h, qkv = norm_linear_decode(x, residual, norm_w, eps, wqkv, bqkv, w_scale=w_scale)
+        h, qkv = norm_linear_decode(x, residual, norm_w, eps, wqkv, bqkv, w_scale=w_scale, fp8_rows=fp8_rows)
         return h, qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_heads, q_override)
     q = torch.empty(1, q_heads, 1, D, dtype=x.dtype, device=x.device)
     h = torch.empty_like(x) if residual is not None else x

@@ -2,7 +2,10 @@
 """tokens/s of the headline configuration (Llama-3.1-8B shapes, 122 K synthetic context, budget 2048, hipGraph, in-place
 layout with overlap_attention, bs 1) with bf16 weights and with weight-only FP8 weights, on one box in one process: the bf16
 model is built and timed, then quantised in place (DecoderLM.quantize_weights) and timed again over the SAME context and
-query walk.  usage: tools/fp8_e2e.py [--steps K] [--warmup W] [--layers L] [--out FILE]   (FILE is appended to)"""
+query walk.  usage: tools/fp8_e2e.py [--steps K] [--warmup W] [--layers L] [--batch B] [--out FILE]   (FILE is appended to)
+--batch B (B > 1): the batched headline configuration (in-place layout, V in pinned host memory, eager decode_step - a captured
+graph at bs > 1 is not part of the FP8 rows work) as a triple over one context, measured one after the other: the bf16 model, the
+FP8 model with the dequantising fallback, the FP8 model with fp8_rows="native" (skv_linear_rows_fp8)."""
 import argparse
 import os
 import sys
@@ -31,13 +34,69 @@ def run(model, ctx, steps, warmup, seed=4242):
     return steps / (time.perf_counter() - t0)
 
 
+def run_eager(model, ctx, steps, warmup, seed=4242):
+    """sequences x steps / s of decode_step on a synthetic query walk (bench.py's --mode eager loop)"""
+    c = model.kv_cache
+    c.kv_offset, c.gen_offset = ctx, 0
+    slack = c.k_cache_buffer.shape[-2] - c.sparse_end
+    walk = llama.QueryWalk(model, step=0.3, seed=seed)
+    tok = torch.randint(0, model.vocab_size, (model.batch_size, 1), device=model.device,
+                        generator=torch.Generator(device=model.device).manual_seed(1))
+    t0 = None
+    for i in range(warmup + steps):
+        if i == warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        if c.gen_offset >= slack:                       # generated-row slack exhausted: rewind the bookkeeping (as bench.py)
+            c.kv_offset, c.gen_offset = ctx, 0
+        walk.advance()
+        tok = model.decode_step(tok, temperature=0.6, q_table=walk.qb)
+        tok[:, -1].tolist()                             # per-step host sync, as the benchmark
+    torch.cuda.synchronize()
+    return steps * model.batch_size / (time.perf_counter() - t0)
+
+
+def batched(a):
+    from shadowkv_amd import tensor_op
+    ctx, dev = 122 * 1024, "cuda:0"
+    model = llama.DecoderLM(cfg=llama.LLAMA_3_1_8B, batch_size=a.batch, max_length=ctx, device=dev, sparse_budget=2048, rank=160,
+                            chunk_size=8, num_layers=a.layers, chunk_layout="inplace", overlap_attention=True,
+                            max_new_tokens=max(1024, 8 * (a.warmup + a.steps) + 256))
+    llama.build_synthetic_context(model, ctx, seed=4321)
+    res = {"bf16": (run_eager(model, ctx, a.steps, a.warmup), model.weight_bytes(), 0, 0)}
+    model.quantize_weights()
+    torch.cuda.empty_cache()
+    for mode in ("fallback", "native"):
+        model.fp8_rows = mode
+        n0, f0 = tensor_op.fp8_native_calls, tensor_op.fp8_fallback_calls
+        tps = run_eager(model, ctx, a.steps, a.warmup)
+        res["fp8 " + mode] = (tps, model.weight_bytes(), tensor_op.fp8_native_calls - n0, tensor_op.fp8_fallback_calls - f0)
+    lines = [f"# tools/fp8_e2e.py --batch {a.batch} on {torch.cuda.get_device_name(0)}: 122 K synthetic context, budget 2048, in-place + "
+             f"overlap_attention, V in pinned host memory, eager decode_step, {model.num_layers} layers, {a.steps} steps after {a.warmup} warm-up steps"]
+    for k, (tps, nbytes, nat, fb) in res.items():
+        lines.append(f"bs {a.batch:2d} {k:<13} {tps:8.2f} tokens/s  weights {nbytes / 1e9:6.2f} GB  native FP8 launches {nat}  "
+                     f"dequantising fallbacks {fb}")
+    lines.append(f"bs {a.batch:2d} tokens/s ratios: fp8 native : bf16 {res['fp8 native'][0] / res['bf16'][0]:.3f}   "
+                 f"fp8 native : fp8 fallback {res['fp8 native'][0] / res['fp8 fallback'][0]:.3f}")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--layers", type=int, default=None)
+    ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.batch > 1:
+        lines = batched(a)
+        print("\n".join(lines))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     ctx, dev = 122 * 1024, "cuda:0"
     model = llama.DecoderLM(cfg=llama.LLAMA_3_1_8B, batch_size=1, max_length=ctx, device=dev, sparse_budget=2048, rank=160,
                             chunk_size=8, num_layers=a.layers, chunk_layout="inplace", overlap_attention=True,

@@ -1,7 +1,86 @@
-"""Event-timed small-M projection kernel (skv_linear_rows_bf16) at the decode shapes, cycling 8 weight copies."""
-import sys, torch
-sys.path.insert(0, ".")
+"""Event-timed small-M projection kernel (skv_linear_rows_bf16) at the decode shapes, cycling 8 weight copies.
+--fp8 [FILE]: the FP8 rows kernel (skv_linear_rows_fp8) against the bf16 launch and the dequantising fallback, HBM-cold."""
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from shadowkv_amd import _lib
+
+
+def fp8_mode(out_path=None, rounds=7, reps=24):
+    """Per layer shape and M in {8, 16, 24, 32}, in ONE process: the FP8 launch, the unchanged skv_linear_rows_bf16 launch on the
+    dequantised matrix and the current fallback (dequantise + F.linear).  The method of tools/time_gemv.py --fp8: per launch a
+    captured graph of `reps` iterations [flush, launch] next to a graph of [flush] alone - the flush rewrites a 1 GiB buffer, so
+    every launch reads its weights from HBM - replayed in interleaved rounds; a launch's time is (its graph - the flush graph)
+    / reps within the round, the reported figure the median over the rounds.  TB/s: over the FP8 bytes (+ 4 N of scales).
+    Acceptance: no FP8 launch slower than the bf16 launch of the same shape and M."""
+    from shadowkv_amd import tensor_op
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(0)
+    flush = torch.zeros(1 << 30, dtype=torch.uint8, device=dev)
+    shapes = [("qkv 6144x4096", 6144, 4096, False), ("o 4096x4096", 4096, 4096, False),
+              ("gate/up 28672x4096 (silu)", 28672, 4096, True), ("down 4096x14336", 4096, 14336, False)]
+
+    def graph_of(fn):
+        st = torch.cuda.Stream()
+        with torch.cuda.stream(st):
+            flush.add_(1)
+            if fn is not None:
+                fn()
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=st):
+            for _ in range(reps):
+                flush.add_(1)
+                if fn is not None:
+                    fn()
+        gr.replay(); torch.cuda.synchronize()
+        return gr
+
+    def timed(gr):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); gr.replay(); e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps           # us per iteration
+
+    med = lambda v: sorted(v)[len(v) // 2]
+    lines = [f"# tools/time_rows_gemm.py --fp8 on {torch.cuda.get_device_name(0)}: HBM-cold launches (1 GiB flush before each), "
+             f"median of {rounds} interleaved rounds of {reps} launches; us per launch, TB/s over the FP8 weight bytes",
+             f"{'shape':<26} {'M':>3} {'fp8 us':>8} {'TB/s':>6} {'bf16 us':>8} {'fallback us':>12} {'bf16/fp8':>9} {'fallback/fp8':>13}"]
+    losers = []
+    for name, n, k, silu in shapes:
+        wb = (torch.randn(n, k, device=dev, generator=g) * 0.02).bfloat16()
+        w8, sc = tensor_op.quantize_fp8_rows(wb)
+        wd = tensor_op.dequantize_fp8_rows(w8, sc)        # the matrix the bf16 launch reads: the same numbers, rounded to bf16
+        del wb
+        g0 = graph_of(None)
+        for M in (8, 16, 24, 32):
+            x = torch.randn(M, 1, k, device=dev, generator=g).bfloat16()
+            y = torch.empty(M, 1, n // 2 if silu else n, device=dev, dtype=torch.bfloat16)
+            g8 = graph_of(lambda: tensor_op.linear_decode(x, w8, fuse_silu_mul=silu, out=y, w_scale=sc, fp8_rows="native"))
+            gb = graph_of(lambda: tensor_op.linear_decode(x, wd, fuse_silu_mul=silu, out=y))
+            gf = graph_of(lambda: tensor_op.linear_decode(x, w8, fuse_silu_mul=silu, out=y, w_scale=sc))
+            t8, tb, tf = [], [], []
+            for _ in range(rounds):
+                f = timed(g0); a = timed(g8); b = timed(gb); c = timed(gf)
+                t8.append(a - f); tb.append(b - f); tf.append(c - f)
+            u8, ub, uf = med(t8), med(tb), med(tf)
+            lines.append(f"{name:<26} {M:3d} {u8:8.2f} {(n * k + 4 * n) / u8 * 1e-6:6.2f} {ub:8.2f} {uf:12.2f} {ub / u8:9.2f} {uf / u8:13.2f}")
+            print(lines[-1], flush=True)
+            if ub < u8:
+                losers.append(f"{name} M {M} ({u8:.2f} us against {ub:.2f} us)")
+            del g8, gb, gf
+        del w8, sc, wd, g0
+    lines.append("# acceptance: " + ("every FP8 launch is no slower than the bf16 launch of the same shape and M" if not losers
+                                     else "AN FP8 LAUNCH IS SLOWER THAN ITS bf16 COUNTERPART: " + "; ".join(losers)))
+    print(lines[-1])
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if "--fp8" in sys.argv:
+    i = sys.argv.index("--fp8")
+    fp8_mode(sys.argv[i + 1] if len(sys.argv) > i + 1 else None)
+    sys.exit(0)
 L = _lib.lib(); dev = "cuda:0"
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 for (N, K, silu) in ((6144, 4096, 0), (4096, 4096, 0), (28672, 4096, 1), (4096, 14336, 0)):
