@@ -31,7 +31,7 @@ def assert_close(got, ref, absv, what=""):
     assert not bool(bad.any()), f"{what}: {int(bad.sum())} elements over the bound, worst excess {float((err - tol).max()):.3g}"
 
 
-def _lists(bs, Hq, L, gen, kind):
+def _lists(bs, Hq, L, gen, kind, device=DEV):
     """Per-head index lists of different sizes (padded with entries >= L, which the kernel ignores)."""
     vs, ss = [], []
     for h in range(Hq):
@@ -50,7 +50,7 @@ def _lists(bs, Hq, L, gen, kind):
         ss.append(s[torch.randperm(s.numel(), generator=gen)])
     pad = lambda xs: torch.stack([torch.cat([x, torch.full((max(map(len, xs)) - len(x),), 2 ** 31 - 1)]) for x in xs])  # noqa
     v, s = pad(vs), pad(ss)
-    return v.expand(bs, -1, -1).contiguous().to(DEV), s.expand(bs, -1, -1).contiguous().to(DEV)
+    return v.expand(bs, -1, -1).contiguous().to(device), s.expand(bs, -1, -1).contiguous().to(device)
 
 
 @pytest.mark.parametrize("bs", [1, 2])
