@@ -12,6 +12,7 @@
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+typedef float f32x2 __attribute__((ext_vector_type(2)));      // two f32 of one packed FMA (v_pk_fma_f32)
 
 // ---- bf16 <-> f32 ---------------------------------------------------------------------
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }

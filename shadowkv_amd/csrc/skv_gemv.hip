@@ -10,32 +10,23 @@
 // 16 B, coalesced), R x 4 row segments are in flight per wave before the first use, x (<= 28 KB) comes from
 // L2.  Per 16 B of weights: 8 conversions + 4 packed FMAs, far below the VALU roof.  Rows are reduced over the
 // 64 lanes with a DPP butterfly + two cross-row shuffles; lane 0 writes.
+//
+// This file holds the bf16 weight stream (prefetch, main loop, K tail) and the bf16 entries.  The frame around the stream -
+// near-pull role, row ownership, row total, epilogue, the launch branch tree - is skv_gemv_frame.h, shared with
+// skv_gemv_fp8.hip; the norm prologue is skv_norm_prologue_4096 (skv_kvproj.h); near_pull_of is in skv_launch.h.
 #include "../../include/shadowkv_hip.h"
-#include "skv_common.h"
-#include "skv_early.h"
-#include "skv_kvproj.h"
+#include "skv_gemv_frame.h"
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef SKV_GEMV_PRE_R2
 #define SKV_GEMV_PRE_R2 4      // k-steps of weights a two-row wave of the NORM variant requests before its norm prologue (round 5: all 8
                                // up front - 142 VGPRs - measured 228.8-230.1 tokens/s against 230.3-231.3 with 4 on one box: not kept)
 #endif
 
 // NORM variant (K == 4096): x is the pre-norm hidden state; every BLOCK recomputes h = x + residual (bf16), the
-// RMS statistics and xn = bf16(h * rstd * w_norm) cooperatively (256 threads x 16 elements, through LDS), so
-// "residual add + RMSNorm + projection" is one launch; block 0 stores h (the new residual stream).  Same
-// element -> thread mapping and reduction tree as skv_add_rmsnorm_kernel: bit-identical to the separate launch.
-// QKV epilogue (QKV == true, W = fused [q; k; v] projection of ONE token, head_dim 128): the wave's 4 rows are two
-// rotation pairs of one head - NeoX: (t, t+64), (t+1, t+65); GLM: (2t', 2t'+1), (2t'+2, 2t'+3) - so lane 0 can rotate
-// q / k at the token's position and write q to q_out and k / v straight into the cache row: the projection, the
-// split, RoPE and update_kv_cache are one launch (same arithmetic as skv_qkv_rope_update_kernel).  N = Hq * 128: the q rows
-// alone (skv_q_gemv_rope) - the k / v rows are then the role of a later launch (skv_kvproj.h).
-// RMAX (lm_head, N % 16 == 0): the workgroup also leaves the LARGEST of its 16 outputs as an order-preserving 16-bit key in
-// range_max[blockIdx.x] - the sampler (skv_sample.hip) then finds the rows that can hold a top-k logit from N / 16 keys
-// instead of streaming all N logits through one CU.
-// NEARP (round 5, the gate/up launch of a ShadowKV layer): the first np.blocks workgroups do not compute - they stage the
-// near misses of this step's selection ahead of the next step (skv_near_pull_role, skv_early.h) while the GEMV streams; the
-// GEMV's own workgroups follow them in the grid.
+// RMS statistics and xn = bf16(h * rstd * w_norm) cooperatively (skv_norm_prologue_4096), so "residual add + RMSNorm +
+// projection" is one launch; block 0 stores h (the new residual stream).  Bit-identical to the separate launch.
+// QKV, N = Hq * 128: the q rows alone (skv_q_gemv_rope) - the k / v rows are then the role of a later launch (skv_kvproj.h).
+// The other template parameters: skv_gemv_frame.h.
 template <int R, bool SILU_PAIR, bool NORM, bool QKV, bool RMAX = false, bool NEARP = false>
 __global__ __launch_bounds__(256) void skv_gemv_kernel(const bf16_t* __restrict__ W, const bf16_t* __restrict__ x,
                                                        const bf16_t* __restrict__ bias, bf16_t* __restrict__ y, int N,
@@ -45,39 +36,17 @@ __global__ __launch_bounds__(256) void skv_gemv_kernel(const bf16_t* __restrict_
                                                        float eps, QkvEpilogue qe, uint16_t* __restrict__ range_max = nullptr,
                                                        NearPull np = NearPull{}) {
     int bx = blockIdx.x;
-    if constexpr (NEARP) {
-        if (bx < np.blocks) {
-            __shared__ int s_near[6 * 64 + 8];
-            skv_near_pull_role(np, bx, threadIdx.x, s_near);
-            return;
-        }
-        bx -= np.blocks;
-    }
+    if (skv_gemv_near_pull_block<NEARP>(np, bx)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ksteps = NORM ? 8 : K / 512;  // 64 lanes x 8 elements per step (NORM: K == 4096, static trip count)
-    // rows of this wave
     int rows[R];
     const int unit0 = (bx * 4 + wave) * (SILU_PAIR ? R / 2 : R);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (SILU_PAIR) rows[r] = (r & 1) ? I + unit0 + r / 2 : unit0 + r / 2;  // (gate, up) pairs
-        else if (QKV && !qe.glm) {
-            // unit0 = R * wave index; a wave owns R/2 rotation pairs (t, t+64) of one head: 128/R waves per head,
-            // rows t0, t0+64, t0+1, t0+65, ...
-            const int w = unit0 / R, head = w / (128 / R), t0 = (R / 2) * (w % (128 / R));
-            rows[r] = head * 128 + t0 + (r >> 1) + ((r & 1) ? 64 : 0);
-        } else rows[r] = unit0 + r;
-    }
-    const int limit = SILU_PAIR ? I : N;
+    skv_gemv_wave_rows<R, SILU_PAIR, QKV>(rows, unit0, I, qe.glm);
+    const int limit = SILU_PAIR ? I : N;      // units of the launch
     if (!NORM && unit0 >= limit) return;   // (NORM: every wave takes part in the block-wide prologue first)
     const bf16_t* wp[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        int row = rows[r];
-        const int base_unit = SILU_PAIR ? unit0 + r / 2 : unit0 + r;
-        if (base_unit >= limit) row = SILU_PAIR ? ((r & 1) ? I : 0) : 0;  // clamp: computed and discarded
-        wp[r] = W + (size_t)row * K + 8 * lane;
-    }
+    for (int r = 0; r < R; ++r) wp[r] = W + (size_t)skv_gemv_stream_row<R, SILU_PAIR>(rows, r, unit0, limit, I) * K + 8 * lane;
     const bf16_t* xp = x + 8 * lane;
     // the first weight segments do not depend on the norm prologue: get them in flight before it
     constexpr int PRE = (NORM && R <= 2) ? SKV_GEMV_PRE_R2 : 4;
@@ -91,52 +60,10 @@ __global__ __launch_bounds__(256) void skv_gemv_kernel(const bf16_t* __restrict_
     }
     f32x2 xn[NORM ? 8 : 1][4];
     if (NORM) {
-        // Block-cooperative prologue: the 256 threads split the 4096 elements exactly like skv_add_rmsnorm_kernel
-        // (thread t owns 16-B vectors t and t + 256, same per-thread order, same wave tree, same (s0+s1)+(s2+s3)),
-        // so h, rstd and xn are bit-identical to the separate launch; xn goes through LDS and every wave picks up
-        // its k-step slices (vector 64 u + lane for step u).  One read of x / residual / w_norm per BLOCK.
+        // xn goes through LDS and every wave picks up its k-step slices (vector 64 u + lane for step u)
         __shared__ u32x4 s_xn[512];
         __shared__ float s_ss[4];
-        // (skv_norm_prologue_4096 in skv_kvproj.h restates this block for the k/v role's wider workgroups: keep the two in step)
-        const int tid = threadIdx.x;
-        u32x4 hx[2];
-        float ss = 0.f;
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int v = tid + it * 256;
-            u32x4 a = reinterpret_cast<const u32x4*>(x)[v];
-            if (residual) {
-                u32x4 c = reinterpret_cast<const u32x4*>(residual)[v];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) a[j] = pack_bf2(bf_lo(a[j]) + bf_lo(c[j]), bf_hi(a[j]) + bf_hi(c[j]));
-            }
-            hx[it] = a;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ss = __builtin_fmaf(bf_lo(a[j]), bf_lo(a[j]), ss);
-                ss = __builtin_fmaf(bf_hi(a[j]), bf_hi(a[j]), ss);
-            }
-        }
-        if (h_out && bx == 0) {
-#pragma unroll
-            for (int it = 0; it < 2; ++it) reinterpret_cast<u32x4*>(h_out)[tid + it * 256] = hx[it];
-        }
-        ss = wave_tree_sum(ss);
-        if (lane == 0) s_ss[wave] = ss;
-        __syncthreads();
-        const float tot = (s_ss[0] + s_ss[1]) + (s_ss[2] + s_ss[3]);
-        const float rstd = 1.0f / sqrtf(tot / (float)K + eps);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int v = tid + it * 256;
-            u32x4 g = reinterpret_cast<const u32x4*>(w_norm)[v];
-            u32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o[j] = pack_bf2(bf_lo(hx[it][j]) * rstd * bf_lo(g[j]), bf_hi(hx[it][j]) * rstd * bf_hi(g[j]));
-            s_xn[v] = o;
-        }
-        __syncthreads();
+        skv_norm_prologue_4096<false>(x, residual, w_norm, bx == 0 ? h_out : nullptr, K, eps, tid, s_xn, s_ss);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const u32x4 o = s_xn[u * 64 + lane];
@@ -196,109 +123,37 @@ __global__ __launch_bounds__(256) void skv_gemv_kernel(const bf16_t* __restrict_
     }
     float tot[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        float s = ((acc[r][0].x + acc[r][0].y) + (acc[r][1].x + acc[r][1].y)) +
-                  ((acc[r][2].x + acc[r][2].y) + (acc[r][3].x + acc[r][3].y));
-        tot[r] = wave_tree_sum(s);
-    }
-    if (QKV) {
-        if (lane == 0 && unit0 < N) skv_qkv_epilogue<R>(qe, bias, rows, tot, unit0);
-        return;
-    }
-    __shared__ uint32_t s_kmax[RMAX ? 4 : 1];
-    if (lane == 0) {
-        if (SILU_PAIR) {
-#pragma unroll
-            for (int p = 0; p < R / 2; ++p) {
-                const int i = unit0 + p;
-                if (i < I) {
-                    const float g = bfr(tot[2 * p]), u = bfr(tot[2 * p + 1]);   // the GEMV outputs are bf16 tensors
-                    y[i] = f2bf(bfr(g / (1.0f + __expf(-g))) * u);
-                }
-            }
-        } else {
-            uint32_t kmax = 0u;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int n = unit0 + r;
-                const bf16_t o = f2bf(bias ? bfr(tot[r]) + bf2f(bias[n < N ? n : 0]) : tot[r]);
-                if (n < N) y[n] = o;
-                if (RMAX) kmax = max(kmax, skv_bf16_order_key(o));
-            }
-            if constexpr (RMAX) s_kmax[wave] = kmax;
-        }
-    }
-    if constexpr (RMAX && !SILU_PAIR && !QKV) {      // (N % 16 == 0: every wave of every workgroup arrives here)
-        __syncthreads();
-        if (tid == 0) range_max[bx] = (uint16_t)max(max(s_kmax[0], s_kmax[1]), max(s_kmax[2], s_kmax[3]));
-    }
+    for (int r = 0; r < R; ++r) tot[r] = skv_gemv_row_total(acc[r]);
+    skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias, y, qe, range_max);
 }
+
+// the bf16 launch of skv_gemv_dispatch
+struct GemvBf16 {
+    static constexpr bool Q_ROWS_ALONE = true;       // N = Hq * 128: skv_q_gemv_rope
+    const bf16_t *W, *x, *bias;
+    bf16_t* y;
+    int N, K;
+    const bf16_t *residual, *w_norm;
+    bf16_t* h_out;
+    float eps;
+    QkvEpilogue qe;
+    hipStream_t st;
+    template <int R, bool SILU, bool NORM, bool QKV, bool RMAX, bool NEARP>
+    void launch(int grid, int I, uint16_t* range_max, const NearPull& near) const {
+        hipLaunchKernelGGL((skv_gemv_kernel<R, SILU, NORM, QKV, RMAX, NEARP>), dim3(grid), dim3(256), 0, st, W, x, bias, y, N, K, I,
+                           residual, w_norm, h_out, eps, qe, range_max, near);
+    }
+};
 
 static int launch_gemv(const void* W, const void* x, const void* bias, void* y, int N, int K, int fuse_silu_mul,
                        const void* residual, const void* w_norm, void* h_out, float eps, bool norm, hipStream_t st,
                        const QkvEpilogue* qkv = nullptr, uint16_t* range_max = nullptr, const NearPull* near = nullptr) {
     if (!W || !x || (!y && !qkv) || N < 1) return SKV_ERR_ARG;
-    QkvEpilogue qe{};
-    if (qkv) qe = *qkv;
     if (K % 8 || K < 512) return SKV_ERR_UNSUPPORTED;
     if (norm && (K != 4096 || !w_norm)) return SKV_ERR_UNSUPPORTED;
-    if (near) {          // a launch of a layer's dense tail with the near-miss pull role in front of its grid
-        if (qkv || range_max || near->blocks < 1 || near->E + SKV_NEAR_SLOTS > 32767) return SKV_ERR_UNSUPPORTED;
-        if (norm && fuse_silu_mul && !(N % 2) && !bias) {                    // gate/up: list 0
-            const int I = N / 2, grid = (I + 7) / 8;
-            hipLaunchKernelGGL((skv_gemv_kernel<4, true, true, false, false, true>), dim3(near->blocks + grid), dim3(256), 0, st,
-                               (const bf16_t*)W, (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, I, (const bf16_t*)residual,
-                               (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe, (uint16_t*)nullptr, *near);
-        } else if (!norm && !fuse_silu_mul && N <= 8192) {                   // down projection (two rows per wave): list 1
-            hipLaunchKernelGGL((skv_gemv_kernel<2, false, false, false, false, true>), dim3(near->blocks + (N + 7) / 8), dim3(256), 0, st,
-                               (const bf16_t*)W, (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, 0, (const bf16_t*)residual,
-                               (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe, (uint16_t*)nullptr, *near);
-        } else {
-            return SKV_ERR_UNSUPPORTED;
-        }
-        return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
-    }
-    if (range_max) {     // the lm_head with the sampler's range keys: norm prologue, whole workgroups of 16 rows
-        if (!norm || qkv || fuse_silu_mul || N % 16) return SKV_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL((skv_gemv_kernel<4, false, true, false, true>), dim3(N / 16), dim3(256), 0, st, (const bf16_t*)W,
-                           (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, 0, (const bf16_t*)residual,
-                           (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe, range_max);
-        return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
-    }
-#define SKV_GEMV(SILU, NORMF, GRID, IARG)                                                                            \
-    hipLaunchKernelGGL((skv_gemv_kernel<4, SILU, NORMF, false>), dim3(GRID), dim3(256), 0, st, (const bf16_t*)W,      \
-                       (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, IARG, (const bf16_t*)residual,        \
-                       (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe)
-    if (qkv) {
-        if (fuse_silu_mul || (N != (qe.Hq + 2 * qe.Hkv) * 128 && N != qe.Hq * 128)) return SKV_ERR_ARG;
-        const int grid = (N + 15) / 16;
-        if (norm)   // one rotation pair per wave: 3,072 waves for N = 6144 (two pairs per wave: 200.4 -> 202.3 tok/s)
-            hipLaunchKernelGGL((skv_gemv_kernel<2, false, true, true>), dim3((N + 7) / 8), dim3(256), 0, st, (const bf16_t*)W,
-                               (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)nullptr, N, K, 0, (const bf16_t*)residual,
-                               (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe);
-        else
-            hipLaunchKernelGGL((skv_gemv_kernel<4, false, false, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)W,
-                               (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)nullptr, N, K, 0, (const bf16_t*)residual,
-                               (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe);
-        return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
-    }
-    if (fuse_silu_mul) {
-        if (N % 2 || bias) return SKV_ERR_ARG;
-        const int I = N / 2;
-        const int grid = (I + 4 * 2 - 1) / (4 * 2);  // 4 waves x 2 (gate, up) pairs
-        if (norm) SKV_GEMV(true, true, grid, I); else SKV_GEMV(true, false, grid, I);
-    } else {
-        const int grid = (N + 4 * 4 - 1) / (4 * 4);
-        if (!norm && N <= 8192) {
-            // few output rows (O and down projections: N = 4096 -> 256 blocks = 1 per CU with 4 rows per wave): 2 rows
-            // per wave doubles the waves and the bytes in flight per CU (measured 198.3 -> 200.7 tok/s; 1 row: 199.3)
-            hipLaunchKernelGGL((skv_gemv_kernel<2, false, false, false>), dim3((N + 7) / 8), dim3(256), 0, st,
-                               (const bf16_t*)W, (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, 0,
-                               (const bf16_t*)residual, (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe);
-        } else if (norm) SKV_GEMV(false, true, grid, 0); else SKV_GEMV(false, false, grid, 0);
-    }
-#undef SKV_GEMV
-    return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
+    const GemvBf16 l{(const bf16_t*)W, (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, (const bf16_t*)residual,
+                     (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qkv ? *qkv : QkvEpilogue{}, st};
+    return skv_gemv_dispatch(l, N, bias != nullptr, fuse_silu_mul != 0, norm, qkv, range_max, near);
 }
 
 extern "C" int skv_gemv_bf16(const void* W, const void* x, const void* bias, void* y, int N, int K, int fuse_silu_mul,
@@ -310,19 +165,6 @@ extern "C" int skv_norm_gemv_bf16(const void* W, const void* x, const void* resi
                                   void* h_out, const void* bias, void* y, int N, int K, int fuse_silu_mul,
                                   skv_stream_t stream) {
     return launch_gemv(W, x, bias, y, N, K, fuse_silu_mul, residual, norm_weight, h_out, eps, true, (hipStream_t)stream);
-}
-
-static int near_pull_of(NearPull& np, void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
-                        const void* v_host, long long host_block_stride, int pull_parts, int list, int active_lists) {
-    if (pull_parts != 1 && pull_parts != 2 && pull_parts != 4) return SKV_ERR_ARG;
-    if (list < 0 || list >= SKV_NEAR_LISTS || active_lists < 1 || active_lists > SKV_NEAR_LISTS || list >= active_lists) return SKV_ERR_ARG;
-    if (!early_state || !v_host || blocks < 1 || groups < 1 || n_landmarks < 1 || n_chunks < 1 || early_max < 1 || early_max > 128 ||
-        (host_block_stride % 8))
-        return SKV_ERR_ARG;
-    if (n_chunks > (1 << 18)) return SKV_ERR_UNSUPPORTED;      // (the early state's limit, skv_select_chunks_fused)
-    const EarlyState es = skv_carve_early(early_state, blocks, groups, n_landmarks, n_chunks, early_max);
-    np = skv_near_pull(es, v_host, host_block_stride, blocks, n_chunks, early_max, pull_parts, list, active_lists);
-    return SKV_OK;
 }
 
 extern "C" int skv_norm_gemv_near_pull_bf16(const void* W, const void* x, const void* residual, const void* norm_weight, float eps,

@@ -8,15 +8,15 @@
 // Same structure as skv_gemv_kernel: a wave owns R weight rows; each wave-instruction reads 1 KiB of a row (64 lanes x 16 B,
 // coalesced, non-temporal), R x 4 row segments are in flight per wave before the first use.  A 16-byte load now holds 16
 // weights: a k-step is 1024 elements, a lane owns elements 16 lane .. 16 lane + 15 of it and reads them from x as two 16-byte
-// vectors.  Per 16 B of weights: 8 v_cvt_pk_f32_fp8 (gfx950 decodes OCP e4m3fn, not MI300's fnuz) + 8 packed FMAs.  The norm
-// prologue is skv_gemv_kernel's, element for element: h and xn are bit-identical to skv_add_rmsnorm; only the pickup of xn from
-// LDS differs (vectors 128 u + 2 lane, 128 u + 2 lane + 1 for step u).
+// vectors.  Per 16 B of weights: 8 v_cvt_pk_f32_fp8 (gfx950 decodes OCP e4m3fn, not MI300's fnuz) + 8 packed FMAs.
+//
+// This file holds the FP8 weight stream (prefetch, main loop, K tail, the row scale) and the FP8 entries.  The frame around
+// the stream - near-pull role, row ownership, row total, epilogue, the launch branch tree - is skv_gemv_frame.h, shared with
+// skv_gemv.hip; the norm prologue is skv_norm_prologue_4096 (skv_kvproj.h): h and xn are bit-identical to skv_add_rmsnorm, only
+// the pickup of xn from LDS differs from the bf16 kernel's (vectors 128 u + 2 lane, 128 u + 2 lane + 1 for step u);
+// near_pull_of is in skv_launch.h.
 #include "../../include/shadowkv_hip.h"
-#include "skv_common.h"
-#include "skv_early.h"
-#include "skv_kvproj.h"
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "skv_gemv_frame.h"
 
 // bytes 0, 1 / bytes 2, 3 of a 32-bit word as two f32 (element order = byte order)
 __device__ __forceinline__ f32x2 e4m3_lo(uint32_t w) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false); }
@@ -42,9 +42,7 @@ __device__ __forceinline__ void bf16x16_to_f32(f32x2 (&xx)[8], const u32x4& a, c
     }
 }
 
-// Template parameters as in skv_gemv_kernel (skv_gemv.hip): R rows per wave, SILU_PAIR (W = [gate; up]), NORM (residual add +
-// RMSNorm prologue, K == 4096), QKV (split + RoPE + cache push in the epilogue), RMAX (the sampler's range keys), NEARP (the
-// near-miss pull role in the launch's first np.blocks workgroups).
+// Template parameters as in skv_gemv_kernel (skv_gemv_frame.h).
 template <int R, bool SILU_PAIR, bool NORM, bool QKV, bool RMAX = false, bool NEARP = false>
 __global__ __launch_bounds__(256) void skv_gemv_fp8_kernel(const uint8_t* __restrict__ W, const float* __restrict__ scale,
                                                            const bf16_t* __restrict__ x, const bf16_t* __restrict__ bias,
@@ -53,36 +51,19 @@ __global__ __launch_bounds__(256) void skv_gemv_fp8_kernel(const uint8_t* __rest
                                                            bf16_t* __restrict__ h_out, float eps, QkvEpilogue qe,
                                                            uint16_t* __restrict__ range_max = nullptr, NearPull np = NearPull{}) {
     int bx = blockIdx.x;
-    if constexpr (NEARP) {
-        if (bx < np.blocks) {
-            __shared__ int s_near[6 * 64 + 8];
-            skv_near_pull_role(np, bx, threadIdx.x, s_near);
-            return;
-        }
-        bx -= np.blocks;
-    }
+    if (skv_gemv_near_pull_block<NEARP>(np, bx)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ksteps = NORM ? 4 : K / 1024;  // 64 lanes x 16 elements per step (NORM: K == 4096, static trip count)
-    // rows of this wave (same ownership as skv_gemv_kernel)
     int rows[R];
     const int unit0 = (bx * 4 + wave) * (SILU_PAIR ? R / 2 : R);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (SILU_PAIR) rows[r] = (r & 1) ? I + unit0 + r / 2 : unit0 + r / 2;  // (gate, up) pairs
-        else if (QKV && !qe.glm) {
-            const int w = unit0 / R, head = w / (128 / R), t0 = (R / 2) * (w % (128 / R));
-            rows[r] = head * 128 + t0 + (r >> 1) + ((r & 1) ? 64 : 0);
-        } else rows[r] = unit0 + r;
-    }
-    const int limit = SILU_PAIR ? I : N;
+    skv_gemv_wave_rows<R, SILU_PAIR, QKV>(rows, unit0, I, qe.glm);
+    const int limit = SILU_PAIR ? I : N;      // units of the launch
     if (!NORM && unit0 >= limit) return;   // (NORM: every wave takes part in the block-wide prologue first)
     const uint8_t* wp[R];
     float sc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        int row = rows[r];
-        const int base_unit = SILU_PAIR ? unit0 + r / 2 : unit0 + r;
-        if (base_unit >= limit) row = SILU_PAIR ? ((r & 1) ? I : 0) : 0;  // clamp: computed and discarded
+        const int row = skv_gemv_stream_row<R, SILU_PAIR>(rows, r, unit0, limit, I);
         wp[r] = W + (size_t)row * K + 16 * lane;
         sc[r] = scale[row];
     }
@@ -98,48 +79,9 @@ __global__ __launch_bounds__(256) void skv_gemv_fp8_kernel(const uint8_t* __rest
     }
     f32x2 xn[NORM ? 4 : 1][8];
     if (NORM) {
-        // Block-cooperative prologue, restated from skv_gemv_kernel (thread t owns 16-B vectors t and t + 256, same per-thread
-        // order, same wave tree, same (s0+s1)+(s2+s3)): h, rstd and xn are bit-identical to skv_add_rmsnorm.
         __shared__ u32x4 s_xn[512];
         __shared__ float s_ss[4];
-        u32x4 hx[2];
-        float ss = 0.f;
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int v = tid + it * 256;
-            u32x4 a = reinterpret_cast<const u32x4*>(x)[v];
-            if (residual) {
-                u32x4 c = reinterpret_cast<const u32x4*>(residual)[v];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) a[j] = pack_bf2(bf_lo(a[j]) + bf_lo(c[j]), bf_hi(a[j]) + bf_hi(c[j]));
-            }
-            hx[it] = a;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ss = __builtin_fmaf(bf_lo(a[j]), bf_lo(a[j]), ss);
-                ss = __builtin_fmaf(bf_hi(a[j]), bf_hi(a[j]), ss);
-            }
-        }
-        if (h_out && bx == 0) {
-#pragma unroll
-            for (int it = 0; it < 2; ++it) reinterpret_cast<u32x4*>(h_out)[tid + it * 256] = hx[it];
-        }
-        ss = wave_tree_sum(ss);
-        if (lane == 0) s_ss[wave] = ss;
-        __syncthreads();
-        const float tot = (s_ss[0] + s_ss[1]) + (s_ss[2] + s_ss[3]);
-        const float rstd = 1.0f / sqrtf(tot / (float)K + eps);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int v = tid + it * 256;
-            u32x4 g = reinterpret_cast<const u32x4*>(w_norm)[v];
-            u32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o[j] = pack_bf2(bf_lo(hx[it][j]) * rstd * bf_lo(g[j]), bf_hi(hx[it][j]) * rstd * bf_hi(g[j]));
-            s_xn[v] = o;
-        }
-        __syncthreads();
+        skv_norm_prologue_4096<false>(x, residual, w_norm, bx == 0 ? h_out : nullptr, K, eps, tid, s_xn, s_ss);
 #pragma unroll
         for (int u = 0; u < 4; ++u) bf16x16_to_f32(xn[u], s_xn[u * 128 + 2 * lane], s_xn[u * 128 + 2 * lane + 1]);
         if (unit0 >= limit) return;
@@ -194,42 +136,8 @@ __global__ __launch_bounds__(256) void skv_gemv_fp8_kernel(const uint8_t* __rest
     }
     float tot[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        float s = ((acc[r][0].x + acc[r][0].y) + (acc[r][1].x + acc[r][1].y)) +
-                  ((acc[r][2].x + acc[r][2].y) + (acc[r][3].x + acc[r][3].y));
-        tot[r] = sc[r] * wave_tree_sum(s);       // the row's scale: one f32 multiply after the reduction
-    }
-    if (QKV) {
-        if (lane == 0 && unit0 < N) skv_qkv_epilogue<R>(qe, bias, rows, tot, unit0);
-        return;
-    }
-    __shared__ uint32_t s_kmax[RMAX ? 4 : 1];
-    if (lane == 0) {
-        if (SILU_PAIR) {
-#pragma unroll
-            for (int p = 0; p < R / 2; ++p) {
-                const int i = unit0 + p;
-                if (i < I) {
-                    const float g = bfr(tot[2 * p]), u = bfr(tot[2 * p + 1]);   // the GEMV outputs are bf16 tensors
-                    y[i] = f2bf(bfr(g / (1.0f + __expf(-g))) * u);
-                }
-            }
-        } else {
-            uint32_t kmax = 0u;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int n = unit0 + r;
-                const bf16_t o = f2bf(bias ? bfr(tot[r]) + bf2f(bias[n < N ? n : 0]) : tot[r]);
-                if (n < N) y[n] = o;
-                if (RMAX) kmax = max(kmax, skv_bf16_order_key(o));
-            }
-            if constexpr (RMAX) s_kmax[wave] = kmax;
-        }
-    }
-    if constexpr (RMAX && !SILU_PAIR && !QKV) {      // (N % 16 == 0: every wave of every workgroup arrives here)
-        __syncthreads();
-        if (tid == 0) range_max[bx] = (uint16_t)max(max(s_kmax[0], s_kmax[1]), max(s_kmax[2], s_kmax[3]));
-    }
+    for (int r = 0; r < R; ++r) tot[r] = sc[r] * skv_gemv_row_total(acc[r]);   // the row's scale: one f32 multiply after the reduction
+    skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias, y, qe, range_max);
 }
 
 // every check of the GEMV's own arguments; host only, before any HIP call
@@ -241,56 +149,35 @@ static int gemv_fp8_args(const void* W, const void* scale, const void* x, const 
     return SKV_OK;
 }
 
+// the FP8 launch of skv_gemv_dispatch
+struct GemvFp8 {
+    static constexpr bool Q_ROWS_ALONE = false;
+    const uint8_t* W;
+    const float* scale;
+    const bf16_t *x, *bias;
+    bf16_t* y;
+    int N, K;
+    const bf16_t *residual, *w_norm;
+    bf16_t* h_out;
+    float eps;
+    QkvEpilogue qe;
+    hipStream_t st;
+    template <int R, bool SILU, bool NORM, bool QKV, bool RMAX, bool NEARP>
+    void launch(int grid, int I, uint16_t* range_max, const NearPull& near) const {
+        hipLaunchKernelGGL((skv_gemv_fp8_kernel<R, SILU, NORM, QKV, RMAX, NEARP>), dim3(grid), dim3(256), 0, st, W, scale, x, bias, y, N,
+                           K, I, residual, w_norm, h_out, eps, qe, range_max, near);
+    }
+};
+
 static int launch_gemv_fp8(const void* W, const void* scale, const void* x, const void* bias, void* y, int N, int K,
                            int fuse_silu_mul, const void* residual, const void* w_norm, void* h_out, float eps, bool norm,
                            hipStream_t st, const QkvEpilogue* qkv = nullptr, uint16_t* range_max = nullptr,
                            const NearPull* near = nullptr) {
     const int rc = gemv_fp8_args(W, scale, x, y, qkv != nullptr, N, K, norm, w_norm);
     if (rc != SKV_OK) return rc;
-    QkvEpilogue qe{};
-    if (qkv) qe = *qkv;
-#define SKV_GEMV8(RR, SILU, NORMF, QKVF, RMAXF, NEARF, GRID, IARG, ...)                                                     \
-    hipLaunchKernelGGL((skv_gemv_fp8_kernel<RR, SILU, NORMF, QKVF, RMAXF, NEARF>), dim3(GRID), dim3(256), 0, st,            \
-                       (const uint8_t*)W, (const float*)scale, (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, IARG, \
-                       (const bf16_t*)residual, (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qe, __VA_ARGS__)
-    if (near) {          // a launch of a layer's dense tail with the near-miss pull role in front of its grid
-        if (qkv || range_max || near->blocks < 1 || near->E + SKV_NEAR_SLOTS > 32767) return SKV_ERR_UNSUPPORTED;
-        if (norm && fuse_silu_mul && !(N % 2) && !bias) {                    // gate/up: list 0
-            const int I = N / 2;
-            SKV_GEMV8(4, true, true, false, false, true, near->blocks + (I + 7) / 8, I, (uint16_t*)nullptr, *near);
-        } else if (!norm && !fuse_silu_mul && N <= 8192) {                   // down projection (two rows per wave): list 1
-            SKV_GEMV8(2, false, false, false, false, true, near->blocks + (N + 7) / 8, 0, (uint16_t*)nullptr, *near);
-        } else {
-            return SKV_ERR_UNSUPPORTED;
-        }
-        return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
-    }
-    if (range_max) {     // the lm_head with the sampler's range keys: norm prologue, whole workgroups of 16 rows
-        if (!norm || qkv || fuse_silu_mul || N % 16) return SKV_ERR_UNSUPPORTED;
-        SKV_GEMV8(4, false, true, false, true, false, N / 16, 0, range_max);
-        return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
-    }
-    if (qkv) {
-        if (fuse_silu_mul || N != (qe.Hq + 2 * qe.Hkv) * 128) return SKV_ERR_ARG;
-        if (norm) SKV_GEMV8(2, false, true, true, false, false, (N + 7) / 8, 0, (uint16_t*)nullptr);    // one rotation pair per wave
-        else SKV_GEMV8(4, false, false, true, false, false, (N + 15) / 16, 0, (uint16_t*)nullptr);
-        return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
-    }
-    if (fuse_silu_mul) {
-        if (N % 2 || bias) return SKV_ERR_ARG;
-        const int I = N / 2;
-        const int grid = (I + 7) / 8;  // 4 waves x 2 (gate, up) pairs
-        if (norm) SKV_GEMV8(4, true, true, false, false, false, grid, I, (uint16_t*)nullptr);
-        else SKV_GEMV8(4, true, false, false, false, false, grid, I, (uint16_t*)nullptr);
-    } else {
-        const int grid = (N + 15) / 16;
-        if (!norm && N <= 8192)    // few output rows (O and down projections): two rows per wave, as the bf16 launch
-            SKV_GEMV8(2, false, false, false, false, false, (N + 7) / 8, 0, (uint16_t*)nullptr);
-        else if (norm) SKV_GEMV8(4, false, true, false, false, false, grid, 0, (uint16_t*)nullptr);
-        else SKV_GEMV8(4, false, false, false, false, false, grid, 0, (uint16_t*)nullptr);
-    }
-#undef SKV_GEMV8
-    return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
+    const GemvFp8 l{(const uint8_t*)W, (const float*)scale, (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K,
+                    (const bf16_t*)residual, (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qkv ? *qkv : QkvEpilogue{}, st};
+    return skv_gemv_dispatch(l, N, bias != nullptr, fuse_silu_mul != 0, norm, qkv, range_max, near);
 }
 
 extern "C" int skv_gemv_fp8(const void* W8, const void* scale, const void* x, const void* bias, void* y, int N, int K,
@@ -327,20 +214,6 @@ extern "C" int skv_qkv_gemv_rope_update_fp8(const void* Wqkv8, const void* scale
                            norm_weight != nullptr, (hipStream_t)stream, &qe);
 }
 
-// (the argument checks and the carving of skv_gemv.hip's near_pull_of, restated: that file stays as it is)
-static int near_pull_fp8_of(NearPull& np, void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
-                            const void* v_host, long long host_block_stride, int pull_parts, int list, int active_lists) {
-    if (pull_parts != 1 && pull_parts != 2 && pull_parts != 4) return SKV_ERR_ARG;
-    if (list < 0 || list >= SKV_NEAR_LISTS || active_lists < 1 || active_lists > SKV_NEAR_LISTS || list >= active_lists) return SKV_ERR_ARG;
-    if (!early_state || !v_host || blocks < 1 || groups < 1 || n_landmarks < 1 || n_chunks < 1 || early_max < 1 || early_max > 128 ||
-        (host_block_stride % 8))
-        return SKV_ERR_ARG;
-    if (n_chunks > (1 << 18)) return SKV_ERR_UNSUPPORTED;      // (the early state's limit, skv_select_chunks_fused)
-    const EarlyState es = skv_carve_early(early_state, blocks, groups, n_landmarks, n_chunks, early_max);
-    np = skv_near_pull(es, v_host, host_block_stride, blocks, n_chunks, early_max, pull_parts, list, active_lists);
-    return SKV_OK;
-}
-
 extern "C" int skv_norm_gemv_near_pull_fp8(const void* W8, const void* scale, const void* x, const void* residual,
                                            const void* norm_weight, float eps, void* h_out, void* y, int N, int K, void* early_state,
                                            int blocks, int groups, int n_landmarks, int n_chunks, int early_max, const void* v_host,
@@ -348,8 +221,8 @@ extern "C" int skv_norm_gemv_near_pull_fp8(const void* W8, const void* scale, co
     int rc = gemv_fp8_args(W8, scale, x, y, false, N, K, true, norm_weight);
     if (rc != SKV_OK) return rc;
     NearPull np{};
-    rc = near_pull_fp8_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, 0,
-                          active_lists);
+    rc = near_pull_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, 0,
+                      active_lists);
     if (rc != SKV_OK) return rc;
     return launch_gemv_fp8(W8, scale, x, nullptr, y, N, K, 1, residual, norm_weight, h_out, eps, true, (hipStream_t)stream, nullptr,
                            nullptr, &np);
@@ -361,8 +234,8 @@ extern "C" int skv_gemv_near_pull_fp8(const void* W8, const void* scale, const v
     int rc = gemv_fp8_args(W8, scale, x, y, false, N, K, false, nullptr);
     if (rc != SKV_OK) return rc;
     NearPull np{};
-    rc = near_pull_fp8_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, list,
-                          SKV_NEAR_LISTS);
+    rc = near_pull_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, list,
+                      SKV_NEAR_LISTS);
     if (rc != SKV_OK) return rc;
     return launch_gemv_fp8(W8, scale, x, bias, y, N, K, 0, nullptr, nullptr, nullptr, 0.f, false, (hipStream_t)stream, nullptr, nullptr,
                            &np);

@@ -1,0 +1,138 @@
+// The frame the decode GEMV kernels share: skv_gemv_kernel (skv_gemv.hip, bf16 weights) and skv_gemv_fp8_kernel
+// (skv_gemv_fp8.hip, e4m3 weights + a row scale) differ only in how they stream and multiply a weight row.  Everything
+// around that stream is stated here once: the near-pull role in front of the grid, which rows a wave owns, a row's
+// reduction, the epilogue, and on the host the branch tree that picks a kernel instance.  The residual add + RMSNorm
+// prologue both kernels call is skv_norm_prologue_4096 (skv_kvproj.h), near_pull_of is next to skv_near_pull (skv_launch.h).
+//
+// Template parameters of both kernels: R rows per wave; SILU_PAIR: W = [gate; up], the wave's rows are R / 2 (gate, up)
+// pairs and y[i] = bf16(silu(gate_i)) * up_i; NORM: x is the pre-norm hidden state (K == 4096); QKV: W = fused [q; k; v] of
+// ONE token (head_dim 128), the wave's rows are R / 2 rotation pairs of one head - NeoX (t, t+64), GLM (2t, 2t+1) - and lane
+// 0 rotates and writes q / the cache row (skv_qkv_epilogue); RMAX (lm_head, N % 16 == 0): the workgroup also leaves the
+// LARGEST of its 16 outputs as an order-preserving 16-bit key in range_max[block] - the sampler (skv_sample.hip) then finds
+// the rows that can hold a top-k logit from N / 16 keys; NEARP: the first np.blocks workgroups do not compute - they stage
+// the near misses of this step's selection ahead of the next step (skv_near_pull_role) while the GEMV streams.
+#pragma once
+#include "skv_common.h"
+#include "skv_early.h"
+#include "skv_kvproj.h"
+
+// NEARP: true for a workgroup of the pull role (it has done its work: the kernel returns); the GEMV's own workgroups follow
+// the role's in the grid and get their index in bx.
+template <bool NEARP>
+__device__ __forceinline__ bool skv_gemv_near_pull_block(const NearPull& np, int& bx) {
+    if constexpr (NEARP) {
+        if (bx < np.blocks) {
+            __shared__ int s_near[6 * 64 + 8];
+            skv_near_pull_role(np, bx, threadIdx.x, s_near);
+            return true;
+        }
+        bx -= np.blocks;
+    }
+    return false;
+}
+
+// The R weight rows of a wave whose first output unit (an output row, or a (gate, up) pair) is unit0 = (bx * 4 + wave) *
+// (SILU_PAIR ? R / 2 : R).
+template <int R, bool SILU_PAIR, bool QKV>
+__device__ __forceinline__ void skv_gemv_wave_rows(int (&rows)[R], int unit0, int I, bool glm) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (SILU_PAIR) rows[r] = (r & 1) ? I + unit0 + r / 2 : unit0 + r / 2;  // (gate, up) pairs
+        else if (QKV && !glm) {
+            // unit0 = R * wave index; a wave owns R/2 rotation pairs (t, t+64) of one head: 128/R waves per head,
+            // rows t0, t0+64, t0+1, t0+65, ...
+            const int w = unit0 / R, head = w / (128 / R), t0 = (R / 2) * (w % (128 / R));
+            rows[r] = head * 128 + t0 + (r >> 1) + ((r & 1) ? 64 : 0);
+        } else rows[r] = unit0 + r;
+    }
+}
+// the row to stream for rows[r]: a row past the end of a ragged last wave (limit = units of the launch) is clamped - computed
+// and discarded
+template <int R, bool SILU_PAIR>
+__device__ __forceinline__ int skv_gemv_stream_row(const int (&rows)[R], int r, int unit0, int limit, int I) {
+    int row = rows[r];
+    const int base_unit = SILU_PAIR ? unit0 + r / 2 : unit0 + r;
+    if (base_unit >= limit) row = SILU_PAIR ? ((r & 1) ? I : 0) : 0;
+    return row;
+}
+
+// a row's dot product from the wave's 64 x 4 packed partial sums: 8 -> 1 per lane, then the wave tree
+__device__ __forceinline__ float skv_gemv_row_total(const f32x2 (&acc)[4]) {
+    const float s = ((acc[0].x + acc[0].y) + (acc[1].x + acc[1].y)) + ((acc[2].x + acc[2].y) + (acc[3].x + acc[3].y));
+    return wave_tree_sum(s);
+}
+
+// tot[R] -> the launch's outputs (lane 0 of every wave writes)
+template <int R, bool SILU_PAIR, bool QKV, bool RMAX>
+__device__ __forceinline__ void skv_gemv_epilogue(const int (&rows)[R], const float (&tot)[R], int unit0, int bx, int tid, int N,
+                                                  int I, const bf16_t* __restrict__ bias, bf16_t* __restrict__ y,
+                                                  const QkvEpilogue& qe, uint16_t* __restrict__ range_max) {
+    const int lane = tid & 63, wave = tid >> 6;
+    if (QKV) {
+        if (lane == 0 && unit0 < N) skv_qkv_epilogue<R>(qe, bias, rows, tot, unit0);
+        return;
+    }
+    __shared__ uint32_t s_kmax[RMAX ? 4 : 1];
+    if (lane == 0) {
+        if (SILU_PAIR) {
+#pragma unroll
+            for (int p = 0; p < R / 2; ++p) {
+                const int i = unit0 + p;
+                if (i < I) {
+                    const float g = bfr(tot[2 * p]), u = bfr(tot[2 * p + 1]);   // the GEMV outputs are bf16 tensors
+                    y[i] = f2bf(bfr(g / (1.0f + __expf(-g))) * u);
+                }
+            }
+        } else {
+            uint32_t kmax = 0u;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int n = unit0 + r;
+                const bf16_t o = f2bf(bias ? bfr(tot[r]) + bf2f(bias[n < N ? n : 0]) : tot[r]);
+                if (n < N) y[n] = o;
+                if (RMAX) kmax = max(kmax, skv_bf16_order_key(o));
+            }
+            if constexpr (RMAX) s_kmax[wave] = kmax;
+        }
+    }
+    if constexpr (RMAX && !SILU_PAIR && !QKV) {      // (N % 16 == 0: every wave of every workgroup arrives here)
+        __syncthreads();
+        if (tid == 0) range_max[bx] = (uint16_t)max(max(s_kmax[0], s_kmax[1]), max(s_kmax[2], s_kmax[3]));
+    }
+}
+
+// Host: the kernel instance and the grid of a launch, for both formats.  L is the format's launcher: it holds the launch's
+// arguments, launch<R, SILU, NORM, QKV, RMAX, NEARP>(grid, I, range_max, near) starts its kernel, and L::Q_ROWS_ALONE says
+// whether the format has the q-only launch (N = Hq * 128).  The format checks its own arguments (pointers, K) before this.
+template <class L>
+static int skv_gemv_dispatch(const L& l, int N, bool bias, bool fuse_silu_mul, bool norm, const QkvEpilogue* qkv, uint16_t* range_max,
+                             const NearPull* near) {
+    const NearPull none{};
+    if (near) {          // a launch of a layer's dense tail with the near-miss pull role in front of its grid
+        if (qkv || range_max || near->blocks < 1 || near->E + SKV_NEAR_SLOTS > 32767) return SKV_ERR_UNSUPPORTED;
+        if (norm && fuse_silu_mul && !(N % 2) && !bias)                      // gate/up: list 0
+            l.template launch<4, true, true, false, false, true>(near->blocks + (N / 2 + 7) / 8, N / 2, nullptr, *near);
+        else if (!norm && !fuse_silu_mul && N <= 8192)                       // down projection (two rows per wave): list 1
+            l.template launch<2, false, false, false, false, true>(near->blocks + (N + 7) / 8, 0, nullptr, *near);
+        else return SKV_ERR_UNSUPPORTED;
+    } else if (range_max) {     // the lm_head with the sampler's range keys: norm prologue, whole workgroups of 16 rows
+        if (!norm || qkv || fuse_silu_mul || N % 16) return SKV_ERR_UNSUPPORTED;
+        l.template launch<4, false, true, false, true, false>(N / 16, 0, range_max, none);
+    } else if (qkv) {
+        if (fuse_silu_mul || (N != (qkv->Hq + 2 * qkv->Hkv) * 128 && !(L::Q_ROWS_ALONE && N == qkv->Hq * 128))) return SKV_ERR_ARG;
+        // norm: one rotation pair per wave: 3,072 waves for N = 6144 (two pairs per wave: 200.4 -> 202.3 tok/s)
+        if (norm) l.template launch<2, false, true, true, false, false>((N + 7) / 8, 0, nullptr, none);
+        else l.template launch<4, false, false, true, false, false>((N + 15) / 16, 0, nullptr, none);
+    } else if (fuse_silu_mul) {
+        if (N % 2 || bias) return SKV_ERR_ARG;
+        const int I = N / 2, grid = (I + 7) / 8;     // 4 waves x 2 (gate, up) pairs
+        if (norm) l.template launch<4, true, true, false, false, false>(grid, I, nullptr, none);
+        else l.template launch<4, true, false, false, false, false>(grid, I, nullptr, none);
+    } else if (!norm && N <= 8192) {
+        // few output rows (O and down projections: N = 4096 -> 256 blocks = 1 per CU with 4 rows per wave): 2 rows
+        // per wave doubles the waves and the bytes in flight per CU (measured 198.3 -> 200.7 tok/s; 1 row: 199.3)
+        l.template launch<2, false, false, false, false, false>((N + 7) / 8, 0, nullptr, none);
+    } else if (norm) l.template launch<4, false, true, false, false, false>((N + 15) / 16, 0, nullptr, none);
+    else l.template launch<4, false, false, false, false, false>((N + 15) / 16, 0, nullptr, none);
+    return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
+}

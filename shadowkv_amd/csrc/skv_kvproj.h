@@ -1,6 +1,7 @@
 // The fused QKV projection of one decode token, split by rows (skv_gemv.hip keeps the q rows as a launch of their own):
-// the RoPE / cache-append epilogue that skv_gemv_kernel's QKV variant shares with the k/v ROLE of a later launch, that
-// kernel's block-cooperative norm prologue restated for workgroups of more than 256 threads, and the role itself.
+// the RoPE / cache-append epilogue that the GEMV kernels' QKV variant (skv_gemv_frame.h) shares with the k/v ROLE of a later
+// launch, the block-cooperative residual add + RMSNorm prologue - the ONE statement of it: both GEMV kernels and the role
+// call it - and the role itself.
 //
 // The landmark scan needs only q, so the k and v rows (2 * Hkv * 128 of the (Hq + 2 Hkv) * 128 weight rows, 16.8 of 50 MB
 // at Llama-3.1-8B) need not stream in front of it: extra workgroups of the scan launch or of the top-k launch compute
@@ -9,8 +10,6 @@
 // k-step order and reduction tree of a row, same epilogue - the cache row holds the same bits.
 #pragma once
 #include "skv_common.h"
-
-typedef float kvp_f32x2 __attribute__((ext_vector_type(2)));
 
 struct QkvEpilogue {
     const bf16_t* cos_sin;
@@ -175,11 +174,11 @@ __device__ __forceinline__ void skv_kv_proj_role(const KvProj& kp, int rb, int t
 #pragma unroll
         for (int r = 0; r < 2; ++r) wv[r][u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wp[r] + (size_t)u * 512));
     skv_norm_prologue_4096<(THREADS > 256)>(kp.h, nullptr, kp.w_norm, nullptr, 4096, kp.eps, tid, s_xn, s_ss);
-    kvp_f32x2 acc[2][4];
+    f32x2 acc[2][4];
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[r][j] = (kvp_f32x2){0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[r][j] = (f32x2){0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < 8; ks += PRE) {
         if (ks > 0) {
@@ -194,10 +193,10 @@ __device__ __forceinline__ void skv_kv_proj_role(const KvProj& kp, int rb, int t
             const u32x4 o = s_xn[(ks + u) * 64 + lane];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const kvp_f32x2 xx = (kvp_f32x2){bf_lo(o[j]), bf_hi(o[j])};
+                const f32x2 xx = (f32x2){bf_lo(o[j]), bf_hi(o[j])};
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
-                    const kvp_f32x2 ww = (kvp_f32x2){bf_lo(wv[r][u][j]), bf_hi(wv[r][u][j])};
+                    const f32x2 ww = (f32x2){bf_lo(wv[r][u][j]), bf_hi(wv[r][u][j])};
                     acc[r][j] = __builtin_elementwise_fma(ww, xx, acc[r][j]);
                 }
             }

@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include "../../include/shadowkv_hip.h"
 
 // attention role of the fused in-place fetch launch (skv_rebuild.hip)
 struct AttnLaunch {
@@ -114,7 +115,10 @@ struct EarlyHooks {
 //   8 KV heads (Llama-3.1-8B 122K): 1 part, 16 requests per thread in flight: 233.9 / 226.9 (+3.0 %); 4 parts: 227.3 / 226.7 (+0.3 %)
 // - the role costs the HBM-bound GEMV it rides in more the harder it pulls: a slow trickle from ~8 CUs is what hides.
 #define SKV_NEAR_LISTS 2
+#ifndef SKV_NEAR_SLOTS         // (include/shadowkv_hip.h states the number for the callers that size the staging)
 #define SKV_NEAR_SLOTS (SKV_NEAR_LISTS * 64)
+#endif
+static_assert(SKV_NEAR_SLOTS == SKV_NEAR_LISTS * 64, "64 staging slots per near-miss list");
 struct EarlyState {
     float* dthr;
     float* finals;
@@ -171,7 +175,7 @@ static inline EarlyHooks skv_early_hooks(const EarlyState& es, int blocks, int g
 }
 
 // Near-miss staging ahead of the next step (round 5): the pull role that rides in the gate/up GEMV launch of a layer
-// (skv_gemv.hip: the first `blocks` workgroups of that launch; skv_near_pull_role in skv_early.h).
+// (skv_gemv_frame.h: the first `blocks` workgroups of that launch; skv_near_pull_role in skv_early.h).
 struct NearPull {
     const int* near_cnt;        // [B]   (top-k launch of this step; the launch's list)
     const int* near_ids;        // [B][SKV_NEAR_MAX]
@@ -197,4 +201,18 @@ static inline NearPull skv_near_pull(const EarlyState& es, const void* v_host, l
                     es.early_of, es.staging, v_host, host_block_stride / 8, B * parts, n_chunks, E, parts, 64 * list,
                     es.near_cnt + (size_t)(1 - list) * B, es.near_ids + (size_t)(1 - list) * B * SKV_NEAR_MAX,
                     es.near_pub + (size_t)(1 - list) * B * SKV_NEAR_MAX};
+}
+// The pull role of a GEMV entry (bf16 and FP8 alike): every check of the role's own arguments, then the carving.  Host only,
+// before any HIP call.
+static inline int near_pull_of(NearPull& np, void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
+                               const void* v_host, long long host_block_stride, int pull_parts, int list, int active_lists) {
+    if (pull_parts != 1 && pull_parts != 2 && pull_parts != 4) return SKV_ERR_ARG;
+    if (list < 0 || list >= SKV_NEAR_LISTS || active_lists < 1 || active_lists > SKV_NEAR_LISTS || list >= active_lists) return SKV_ERR_ARG;
+    if (!early_state || !v_host || blocks < 1 || groups < 1 || n_landmarks < 1 || n_chunks < 1 || early_max < 1 || early_max > 128 ||
+        (host_block_stride % 8))
+        return SKV_ERR_ARG;
+    if (n_chunks > (1 << 18)) return SKV_ERR_UNSUPPORTED;      // (the early state's limit, skv_select_chunks_fused)
+    const EarlyState es = skv_carve_early(early_state, blocks, groups, n_landmarks, n_chunks, early_max);
+    np = skv_near_pull(es, v_host, host_block_stride, blocks, n_chunks, early_max, pull_parts, list, active_lists);
+    return SKV_OK;
 }

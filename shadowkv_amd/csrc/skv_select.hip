@@ -33,7 +33,6 @@ __device__ unsigned long long* g_score_stamps;
 #else
 #define SCORE_STAMP(i)
 #endif
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------
 // K1: scoring.  One workgroup (4 waves) per 256-landmark tile.  A wave-instruction loads

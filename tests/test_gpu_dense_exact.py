@@ -165,6 +165,62 @@ def test_norm_gemv_range_max_exact(N):
         assert bool((keys[:, N // 16:] == -1).all()), "a key written past N / 16"
 
 
+def near_cache():
+    """A fresh early state as test_gpu_gemv_fp8_exact's near-pull test builds it (8 KV heads, 16,384 tokens, two near-miss lists)
+    after one selection step: its near-miss lists are what the pull role of a launch stages; no launch has staged into it."""
+    from test_gpu_kv_cache import _headline_cache
+    c, cs, g = _headline_cache(8, False, L=16384, seed=41)
+    c.near_lists = 2
+    c.enable_early_fetch(near=True)
+    q = (torch.randn(1, 32, 1, 128, device=DEV, generator=g) * 1.5).bfloat16()
+    c.select_fetch_attend_inplace(0, q, cs, kv_len=c.sparse_end + 2)
+    torch.cuda.synchronize()
+    return c
+
+
+@pytest.mark.parametrize("launch", ["gate_up", "down"])
+def test_near_pull_launches_change_no_bit(launch):
+    """skv_norm_gemv_near_pull_bf16 (gate/up, K = 4096, I = 9) and skv_gemv_near_pull_bf16 (down, N = 9, K = 520: ragged last
+    workgroup, a K tail): y and h bit-equal to the launch without the pull role in front of its grid, and the role staged."""
+    _lib, L, st = _L()
+    p = _lib.ptr
+    c = near_cache()
+    if launch == "gate_up":
+        I, K = 9, 4096
+        n = norm_on_device(K, seed=I, residual=True)
+        bank = dr.pair_bank(I, K, seed=I + K, colsign=n["h"] // 2)
+        w = weights_on_device(bank)
+        y0, h0, _ = run_gemv(bank, w, n["x_d"], None, silu=True, norm=n, eps=1e-5)
+        args = c.near_pull_args(0)
+        assert args is not None
+        y1, h1 = sentinel_buf(bank.launches, I + PAD), sentinel_buf(K + PAD)
+        for l in range(bank.launches):
+            rc = L.skv_norm_gemv_near_pull_bf16(p(w[l * 2 * I:(l + 1) * 2 * I]), p(n["x_d"]), p(n["res_d"]), p(n["w_d"]), 1e-5, p(h1),
+                                                p(y1[l]), 2 * I, K, *args, st)
+            assert rc == 0, rc
+        torch.cuda.synchronize()
+        check_h(h1, n, "near-pull gate/up")
+        assert torch.equal(h0.view(torch.int16), h1.view(torch.int16))
+    else:
+        N, K = 9, 520
+        bank = dr.plain_bank(N, K, seed=N + K)
+        w = weights_on_device(bank)
+        xi, _ = dr.structured_x(1, K, seed=K)
+        x, bias = dev16(xi), dev16(dr.integer_bias(N, seed=N))
+        y0, _, _ = run_gemv(bank, w, x, bias, silu=False)
+        args = c.near_pull_args(0, 1)
+        assert args is not None and args[-1] == 1
+        y1 = sentinel_buf(bank.launches, N + PAD)
+        for l in range(bank.launches):
+            rc = L.skv_gemv_near_pull_bf16(p(w[l * N:(l + 1) * N]), p(x), p(bias), p(y1[l]), N, K, *args, st)
+            assert rc == 0, rc
+        torch.cuda.synchronize()
+        assert_bits(y1[:, :N], dr.gemv_ref(bank, xi, dr.integer_bias(N, seed=N))[0], "near-pull down")
+    assert torch.equal(y0.view(torch.int16), y1.view(torch.int16)), "the pull role changed an output bit (sentinels included)"
+    own = c.near_published_ids(0)[:, 64:] if launch == "down" else c.near_published_ids(0)[:, :64]     # the launch's own list
+    assert int((own >= 0).sum()) > 0, "the pull role staged no chunk of its list"
+
+
 # ---------------------------------------------------------------------------------------------- QKV epilogue, k/v role
 ROWS = 12                        # cache rows per head
 CS_ROWS = 40

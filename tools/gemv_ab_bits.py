@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""Bit identity of the decode GEMV entries between two builds of the library.
+
+    SKV_LIB_PATH=<library A> python tools/gemv_ab_bits.py --dump a.pt      (one fresh process per library)
+    python tools/gemv_ab_bits.py --dump b.pt
+    python tools/gemv_ab_bits.py --compare a.pt b.pt
+
+--dump runs every public GEMV entry of both formats (skv_gemv.hip, skv_gemv_fp8.hip) on seeded inputs - the shapes of the
+exact tests and the Llama-3.1-8B shapes - and stores every output tensor as raw 16-bit words; --compare is torch.equal."""
+import os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")]
+import torch
+
+DEV = "cuda:0"
+
+
+def dump(path):
+    from shadowkv_amd import _lib, tensor_op
+    L, p, st = _lib.lib(), _lib.ptr, _lib.current_stream_handle()
+    g = torch.Generator(device=DEV).manual_seed(7)
+    out = {}
+
+    def rnd(*shape, s=1.0):
+        return (torch.randn(*shape, device=DEV, generator=g) * s).bfloat16()
+
+    def buf(n):
+        return torch.full((n + 8,), 1000.0, dtype=torch.bfloat16, device=DEV)
+
+    def keep(name, rc, *ts):
+        assert rc == 0, (name, rc)
+        torch.cuda.synchronize()
+        for i, t in enumerate(ts):
+            out[f"{name}/{i}"] = t.view(torch.int16).cpu().clone()
+
+    def both(N, K):
+        w = rnd(N, K, s=0.02)
+        w8, sc = tensor_op.quantize_fp8_rows(w)
+        return w, w8, sc
+
+    # plain / bias / SiLU pair (no norm): the shapes of the exact tests, then O, down and gate/up of Llama-3.1-8B
+    for N, K in [(1, 512), (7, 520), (9, 1024), (20, 1040), (4101, 13696), (8193, 1000), (8208, 1024), (8209, 512), (4096, 4096),
+                 (4096, 14336), (2006, 13696), (28672, 4096)]:
+        w, w8, sc = both(N, K)
+        x, b = rnd(K), rnd(N)
+        for bias in (None, b):
+            y = buf(N)
+            keep(f"gemv_bf16 {N}x{K} bias {bias is not None}", L.skv_gemv_bf16(p(w), p(x), p(bias), p(y), N, K, 0, st), y)
+            if K % 16 == 0 and K >= 1024:
+                y = buf(N)
+                keep(f"gemv_fp8 {N}x{K} bias {bias is not None}", L.skv_gemv_fp8(p(w8), p(sc), p(x), p(bias), p(y), N, K, 0, st), y)
+        if N % 2 == 0:
+            y = buf(N // 2)
+            keep(f"gemv_bf16 silu {N}x{K}", L.skv_gemv_bf16(p(w), p(x), 0, p(y), N, K, 1, st), y)
+            if K % 16 == 0 and K >= 1024:
+                y = buf(N // 2)
+                keep(f"gemv_fp8 silu {N}x{K}", L.skv_gemv_fp8(p(w8), p(sc), p(x), 0, p(y), N, K, 1, st), y)
+    # norm prologue: plain / bias / SiLU pair, with and without a residual; range keys (lm_head)
+    K = 4096
+    x, res, nw = rnd(K), rnd(K), (1 + 0.1 * torch.randn(K, device=DEV, generator=g)).bfloat16()
+    for N in (1, 17, 20, 4101, 8193, 2 * 1003, 6144, 28672):
+        w, w8, sc = both(N, K)
+        b = rnd(N)
+        for r in (res, None):
+            for bias in (None, b):
+                for silu in ((0, 1) if N % 2 == 0 and bias is None else (0,)):
+                    No = N // 2 if silu else N
+                    tag = f"{N}x{K} residual {r is not None} bias {bias is not None} silu {silu}"
+                    y, h = buf(No), buf(K)
+                    keep("norm_gemv_bf16 " + tag, L.skv_norm_gemv_bf16(p(w), p(x), p(r), p(nw), 1e-5, p(h), p(bias), p(y), N, K, silu, st), y, h)
+                    y, h = buf(No), buf(K)
+                    keep("norm_gemv_fp8 " + tag,
+                         L.skv_norm_gemv_fp8(p(w8), p(sc), p(x), p(r), p(nw), 1e-5, p(h), p(bias), p(y), N, K, silu, st), y, h)
+    for N in (16, 48, 32000, 128256):
+        w, w8, sc = both(N, K)
+        b = rnd(N)
+        for bias in (None, b):
+            y, h, keys = buf(N), buf(K), torch.full((N // 16 + 8,), -1, dtype=torch.int16, device=DEV)
+            keep(f"rangemax_bf16 {N} bias {bias is not None}",
+                 L.skv_norm_gemv_rangemax_bf16(p(w), p(x), p(res), p(nw), 1e-5, p(h), p(bias), p(y), N, K, p(keys), st), y, h, keys)
+            y, h, keys = buf(N), buf(K), torch.full((N // 16 + 8,), -1, dtype=torch.int16, device=DEV)
+            keep(f"rangemax_fp8 {N} bias {bias is not None}",
+                 L.skv_norm_gemv_rangemax_fp8(p(w8), p(sc), p(x), p(res), p(nw), 1e-5, p(h), p(bias), p(y), N, K, p(keys), st), y, h, keys)
+        del w, w8, sc
+    # QKV epilogue (norm K = 4096, plain K = 1040 and bf16 K = 520), NeoX and GLM; the q-only launch
+    ROWS, CS = 12, 40
+    for Hq, Hkv, glm in ((32, 8, False), (4, 1, False), (32, 4, True), (2, 1, True)):
+        N = (Hq + 2 * Hkv) * 128
+        cs = (torch.rand(CS, 64 if glm else 128, device=DEV, generator=g) * 2 - 1).bfloat16()
+        pos, row, ov = torch.tensor([17], device=DEV), torch.tensor([5], device=DEV), rnd(Hq * 128)
+        for Kq in (4096, 1040, 520):
+            w, w8, sc = both(N, Kq)
+            xq, b = rnd(Kq), rnd(N)
+            norm = Kq == 4096
+            for bias in (None, b):
+                for override in (None, ov):
+                    for fmt in ("bf16", "fp8") if Kq != 520 else ("bf16",):
+                        q, h = buf(Hq * 128), buf(Kq)
+                        kc = torch.zeros(1, Hkv, ROWS, 128, device=DEV, dtype=torch.bfloat16)
+                        vc = torch.zeros_like(kc)
+                        tail = (p(res) if norm else 0, p(nw) if norm else 0, 1e-5, p(h) if norm else 0, p(bias), p(cs), p(pos), p(row),
+                                p(override), p(q), p(kc), p(vc), Kq, Hq, Hkv, 128, cs.stride(0), CS, kc.stride(1), ROWS, 2 if glm else 1, st)
+                        rc = L.skv_qkv_gemv_rope_update(p(w), p(xq), *tail) if fmt == "bf16" else \
+                            L.skv_qkv_gemv_rope_update_fp8(p(w8), p(sc), p(xq), *tail)
+                        keep(f"qkv_{fmt} Hq {Hq} Hkv {Hkv} glm {glm} K {Kq} bias {bias is not None} override {override is not None}",
+                             rc, q, h, kc, vc)
+                    if norm:
+                        q, h = buf(Hq * 128), buf(Kq)
+                        keep(f"q_only Hq {Hq} Hkv {Hkv} glm {glm} bias {bias is not None} override {override is not None}",
+                             L.skv_q_gemv_rope(p(w), p(xq), p(res), p(nw), 1e-5, p(h), p(bias), p(cs), p(pos), p(override), p(q), Kq, Hq, Hkv,
+                                               128, cs.stride(0), CS, 2 if glm else 1, st), q, h)
+    # near-pull launches: gate/up (list 0) and down (list 1) in front of an early state after one selection step
+    from test_gpu_kv_cache import _headline_cache
+    for fmt in ("bf16", "fp8"):
+        c, cs, gc = _headline_cache(8, False, L=16384, seed=41)
+        c.near_lists = 2
+        c.enable_early_fetch(near=True)
+        qq = (torch.randn(1, 32, 1, 128, device=DEV, generator=gc) * 1.5).bfloat16()
+        c.select_fetch_attend_inplace(0, qq, cs, kv_len=c.sparse_end + 2)
+        torch.cuda.synchronize()
+        gs = torch.Generator(device=DEV).manual_seed(9)
+        for N, Kd in ((18, 4096), (28672, 4096)):
+            w = (torch.randn(N, Kd, device=DEV, generator=gs) * 0.02).bfloat16()
+            w8, sc = tensor_op.quantize_fp8_rows(w)
+            y, h = buf(N // 2), buf(Kd)
+            a = c.near_pull_args(0)
+            rc = L.skv_norm_gemv_near_pull_bf16(p(w), p(x), p(res), p(nw), 1e-5, p(h), p(y), N, Kd, *a, st) if fmt == "bf16" else \
+                L.skv_norm_gemv_near_pull_fp8(p(w8), p(sc), p(x), p(res), p(nw), 1e-5, p(h), p(y), N, Kd, *a, st)
+            keep(f"near gate/up {fmt} {N}", rc, y, h, c.near_published_ids(0).to(torch.int32).view(torch.int16))
+        for N, Kd in ((9, 1040), (4096, 14336)):
+            w = (torch.randn(N, Kd, device=DEV, generator=gs) * 0.02).bfloat16()
+            w8, sc = tensor_op.quantize_fp8_rows(w)
+            xd, b = (torch.randn(Kd, device=DEV, generator=gs)).bfloat16(), (torch.randn(N, device=DEV, generator=gs)).bfloat16()
+            y = buf(N)
+            a = c.near_pull_args(0, 1)
+            rc = L.skv_gemv_near_pull_bf16(p(w), p(xd), p(b), p(y), N, Kd, *a, st) if fmt == "bf16" else \
+                L.skv_gemv_near_pull_fp8(p(w8), p(sc), p(xd), p(b), p(y), N, Kd, *a, st)
+            keep(f"near down {fmt} {N}", rc, y, c.near_published_ids(0).to(torch.int32).view(torch.int16))
+        del c
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(out, path)
+    print(f"{len(out)} tensors from {_lib.LIB_PATH} -> {path}")
+
+
+def compare(a_path, b_path):
+    a, b = torch.load(a_path), torch.load(b_path)
+    assert a.keys() == b.keys(), "the two dumps hold different entries"
+    bad = [k for k in a if not torch.equal(a[k], b[k])]
+    for k in bad:
+        print(f"DIFFERENT  {k}: {int((a[k] != b[k]).sum())} of {a[k].numel()} words")
+    groups = {}
+    for k in a:
+        groups.setdefault(k.split(" ")[0], []).append(k)
+    for name, ks in groups.items():
+        print(f"{name:<22} {len(ks):4d} tensors  {'EQUAL' if not any(k in bad for k in ks) else 'DIFFERENT'}")
+    print(f"{len(a) - len(bad)} of {len(a)} tensors bit-identical")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--dump":
+        dump(sys.argv[2])
+    elif len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    else:
+        sys.exit(__doc__)
