@@ -672,6 +672,39 @@ SKV_EXPORT int skv_gemv_near_pull_fp8(const void* W8, const void* scale, const v
 SKV_EXPORT int skv_linear_rows_fp8(const void* W8, const void* scale, const void* X, const void* bias, void* Y, int M, int N, int K,
                         int fuse_silu_mul, skv_stream_t stream);
 
+/* FP8 (OCP e4m3fn) V offload table.  The chunk table holds bytes instead of bf16 - a chunk row is
+ * 8 token rows x 128 bytes = 1 KiB - and one f32 power-of-two scale per token row lives in a device tensor
+ * v_scale [blocks][scale_block_stride] (8 consecutive scales per chunk).  Per token row v[0..127]:
+ *     amax = max |v[d]|;  scale = the smallest power of two with amax / scale <= 448, clamped to [2^-100, 2^100] (amax == 0: 1);
+ *     byte[d] = e4m3fn(RNE(clamp(f32(v[d]) / scale, -448, 448)));   v'[d] = bf16(scale * f32(e4m3(byte[d])))  (exact).
+ * skv_quantize_v_rows: v bf16 [batch_size][heads][tokens][128] through element strides (the last dimension contiguous,
+ *   strides multiples of 8, v 16-byte aligned) -> table bytes and scales of `tokens` consecutive token rows per (batch, head);
+ *   table_block_stride (bytes, multiple of 8, >= tokens * 128) and scale_block_stride (>= tokens) separate the blocks.
+ * skv_land_chunks_fp8 / skv_fetch_kv_fp8 / skv_fetch_kv_inplace_fp8: skv_land_chunks / skv_fetch_kv / skv_fetch_kv_inplace
+ *   with host_values / v_host the byte table (host_block_stride in bytes, a multiple of 16) and v_scale /
+ *   scale_block_stride (a multiple of 8) in front of the stream.  Rows read from the table are dequantised on the way into
+ *   the cache; moved hits are bf16 already.  The fetch entries take rank 160 and chunk_size 8 (else SKV_ERR_UNSUPPORTED).
+ * A null table, a null v_scale or a misaligned stride: SKV_ERR_ARG, checked on the host before any HIP call. */
+SKV_EXPORT int skv_quantize_v_rows(const void* v, long long stride_b, long long stride_h, long long stride_t, int batch_size,
+                        int heads, int tokens, int head_dim, void* table, long long table_block_stride, float* scale,
+                        long long scale_block_stride, skv_stream_t stream);
+SKV_EXPORT int skv_land_chunks_fp8(const void* host_values, void* cache_buffer, const void* temp, const int32_t* offsets,
+                        const int32_t* cnts, long long host_block_stride, long long cache_block_stride,
+                        long long cache_sparse_offset, int blocks, int select_sets, const float* v_scale,
+                        long long scale_block_stride, skv_stream_t stream);
+SKV_EXPORT int skv_fetch_kv_fp8(const void* U, const void* SV, const void* cos_sin, const int64_t* chunk_ids, const int32_t* cnts,
+                     const int32_t* offsets, void* k_cache, const void* k_temp, const void* v_host, void* v_cache,
+                     const void* v_temp, int batch_size, int heads, int seq_len, int head_dim, int rank, int select_sets,
+                     int chunk_size, long long cos_sin_stride, long long cache_stride_b, long long cache_stride_h,
+                     long long cache_stride_s, int sparse_start, int rope_mode, long long host_block_stride,
+                     const float* v_scale, long long scale_block_stride, skv_stream_t stream);
+SKV_EXPORT int skv_fetch_kv_inplace_fp8(const void* U, const void* SV, const void* cos_sin, const int32_t* miss_ids,
+                             const int32_t* dst_slots, const int32_t* cnts, void* k_cache, const void* v_host, void* v_cache,
+                             int batch_size, int heads, int seq_len, int head_dim, int rank, int select_sets, int chunk_size,
+                             long long cos_sin_stride, long long cache_stride_b, long long cache_stride_h,
+                             long long cache_stride_s, int sparse_start, int rope_mode, long long host_block_stride,
+                             const float* v_scale, long long scale_block_stride, skv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,11 @@ _SIGS = {
     "skv_qkv_gemv_rope_update_fp8": (c_int, [c_p] * 5 + [c_f] + [c_p] * 9 + [c_int] * 4 + [c_ll, c_int, c_ll] + [c_int] * 2 + [c_p]),
     "skv_norm_gemv_near_pull_fp8": (c_int, [c_p] * 5 + [c_f] + [c_p] * 2 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
     "skv_gemv_near_pull_fp8": (c_int, [c_p] * 5 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
+    # FP8 (e4m3) V offload table: the bf16 entries with (v_scale, scale_block_stride) in front of the stream
+    "skv_quantize_v_rows": (c_int, [c_p] + [c_ll] * 3 + [c_int] * 4 + [c_p, c_ll, c_p, c_ll, c_p]),
+    "skv_land_chunks_fp8": (c_int, [c_p] * 5 + [c_ll] * 3 + [c_int] * 2 + [c_p, c_ll, c_p]),
+    "skv_fetch_kv_fp8": (c_int, [c_p] * 11 + [c_int] * 7 + [c_ll] * 4 + [c_int] * 2 + [c_ll, c_p, c_ll, c_p]),
+    "skv_fetch_kv_inplace_fp8": (c_int, [c_p] * 9 + [c_int] * 7 + [c_ll] * 4 + [c_int] * 2 + [c_ll, c_p, c_ll, c_p]),
     "skv_chunk_stats": (c_int, [c_p, c_ll] + [c_int] * 4 + [c_p] * 3),
     "skv_host_alloc": (c_int, [ctypes.POINTER(c_p), c_sz]),
     "skv_host_free": (c_int, [c_p]),

@@ -37,7 +37,8 @@ int skv_launch_rebuild(const void* U, const void* SV, const void* cos_sin, const
                        long long out_stride_s, int out_row0, int mode, const void* hit_temp, const int32_t* hit_offsets,
                        const int32_t* dst_slots, const void* v_host, void* v_buf, const void* v_temp,
                        long long v_host_stride, long long v_stride, long long v_off, hipStream_t st,
-                       const AttnLaunch* attn, const EarlyConsume* early = nullptr);
+                       const AttnLaunch* attn, const EarlyConsume* early = nullptr, const float* v_scale = nullptr,
+                       long long v_scale_stride = 0);
 int skv_launch_attn_merge(const void* ws, const int32_t* cnts, void* out, int bs, int Hq, int Hkv, int S, int splits,
                           hipStream_t st);
 int skv_launch_stage_hits(void* k_buf, void* k_temp, void* v_buf, void* v_temp, const int32_t* offsets,
@@ -46,6 +47,12 @@ int skv_launch_stage_hits(void* k_buf, void* k_temp, void* v_buf, void* v_temp, 
 int skv_launch_land_rows(const void* host_rows, void* buf, const void* temp, const int32_t* offsets,
                          const int32_t* cnts, long long host_len_elems, long long stride_elems, long long off_elems,
                          int B, int S, hipStream_t st);
+int skv_launch_land_rows_fp8(const void* host_rows, const float* v_scale, void* buf, const void* temp, const int32_t* offsets,
+                             const int32_t* cnts, long long host_len_elems, long long scale_stride, long long stride_elems,
+                             long long off_elems, int B, int S, hipStream_t st);
+int skv_launch_quantize_v_rows(const void* v, long long stride_b, long long stride_h, long long stride_t, int batch_size,
+                               int heads, int tokens, int head_dim, void* table, long long table_block_stride, float* scale,
+                               long long scale_block_stride, hipStream_t st);
 int skv_launch_sparse_attention(const void* q, const void* k, const void* v, void* out, void* ws,
                                 const int* kv_len_dev, int kv_len_host, int kv_rows, long long kv_stride_h, int bs, int Hq,
                                 int Hkv, int head_dim, int splits, float scale, const int32_t* slots, int n_slots,
@@ -700,6 +707,58 @@ int skv_land_chunks(const void* host_values, void* cache_buffer, const void* tem
     return finish(skv_launch_land_rows(host_values, cache_buffer, temp, offsets, cnts, host_block_stride,
                                        cache_block_stride, cache_sparse_offset, blocks, select_sets,
                                        (hipStream_t)stream));
+}
+
+// ---- FP8 (e4m3) V offload table: the bf16 entries with the table's f32 scales behind their arguments
+int skv_quantize_v_rows(const void* v, long long stride_b, long long stride_h, long long stride_t, int batch_size, int heads,
+                        int tokens, int head_dim, void* table, long long table_block_stride, float* scale,
+                        long long scale_block_stride, skv_stream_t stream) {
+    return finish(skv_launch_quantize_v_rows(v, stride_b, stride_h, stride_t, batch_size, heads, tokens, head_dim, table,
+                                             table_block_stride, scale, scale_block_stride, (hipStream_t)stream));
+}
+
+int skv_land_chunks_fp8(const void* host_values, void* cache_buffer, const void* temp, const int32_t* offsets,
+                        const int32_t* cnts, long long host_block_stride, long long cache_block_stride,
+                        long long cache_sparse_offset, int blocks, int select_sets, const float* v_scale,
+                        long long scale_block_stride, skv_stream_t stream) {
+    if (!host_values || !v_scale || !cache_buffer || !temp || !offsets || !cnts) return SKV_ERR_ARG;
+    return finish(skv_launch_land_rows_fp8(host_values, v_scale, cache_buffer, temp, offsets, cnts, host_block_stride,
+                                           scale_block_stride, cache_block_stride, cache_sparse_offset, blocks, select_sets,
+                                           (hipStream_t)stream));
+}
+
+int skv_fetch_kv_fp8(const void* U, const void* SV, const void* cos_sin, const int64_t* chunk_ids, const int32_t* cnts,
+                     const int32_t* offsets, void* k_cache, const void* k_temp, const void* v_host, void* v_cache,
+                     const void* v_temp, int batch_size, int heads, int seq_len, int head_dim, int rank, int select_sets,
+                     int chunk_size, long long cos_sin_stride, long long cache_stride_b, long long cache_stride_h,
+                     long long cache_stride_s, int sparse_start, int rope_mode, long long host_block_stride,
+                     const float* v_scale, long long scale_block_stride, skv_stream_t stream) {
+    if (!U || !SV || !cos_sin || !chunk_ids || !cnts || !offsets || !k_cache || !k_temp || !v_host || !v_cache || !v_temp || !v_scale)
+        return SKV_ERR_ARG;
+    if ((rope_mode != 1 && rope_mode != 2) || (host_block_stride % 16) || (scale_block_stride % 8)) return SKV_ERR_ARG;
+    if (chunk_size != 8) return SKV_ERR_UNSUPPORTED;
+    return finish(skv_launch_rebuild(U, SV, cos_sin, chunk_ids, 1, cnts, k_cache, batch_size, heads, seq_len, head_dim,
+                                     rank, select_sets, chunk_size, cos_sin_stride, cache_stride_b, cache_stride_h,
+                                     cache_stride_s, sparse_start, rope_mode, k_temp, offsets, nullptr, v_host, v_cache, v_temp,
+                                     host_block_stride, cache_stride_h, (long long)sparse_start * head_dim,
+                                     (hipStream_t)stream, nullptr, nullptr, v_scale, scale_block_stride));
+}
+
+int skv_fetch_kv_inplace_fp8(const void* U, const void* SV, const void* cos_sin, const int32_t* miss_ids,
+                             const int32_t* dst_slots, const int32_t* cnts, void* k_cache, const void* v_host, void* v_cache,
+                             int batch_size, int heads, int seq_len, int head_dim, int rank, int select_sets, int chunk_size,
+                             long long cos_sin_stride, long long cache_stride_b, long long cache_stride_h,
+                             long long cache_stride_s, int sparse_start, int rope_mode, long long host_block_stride,
+                             const float* v_scale, long long scale_block_stride, skv_stream_t stream) {
+    if (!U || !SV || !cos_sin || !miss_ids || !dst_slots || !cnts || !k_cache || !v_host || !v_cache || !v_scale) return SKV_ERR_ARG;
+    if ((rope_mode != 1 && rope_mode != 2) || (host_block_stride % 16) || (scale_block_stride % 8)) return SKV_ERR_ARG;
+    if (chunk_size != 8) return SKV_ERR_UNSUPPORTED;
+    return finish(skv_launch_rebuild(U, SV, cos_sin, miss_ids, 0, cnts, k_cache, batch_size, heads, seq_len, head_dim,
+                                     rank, select_sets, chunk_size, cos_sin_stride, cache_stride_b, cache_stride_h,
+                                     cache_stride_s, sparse_start, rope_mode, nullptr, miss_ids, dst_slots, v_host,
+                                     v_cache, nullptr, host_block_stride, cache_stride_h,
+                                     (long long)sparse_start * head_dim, (hipStream_t)stream, nullptr, nullptr, v_scale,
+                                     scale_block_stride));
 }
 
 int skv_sparse_attention(const void* q, const void* k, const void* v, void* out, void* workspace,

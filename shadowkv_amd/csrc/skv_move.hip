@@ -18,6 +18,7 @@
 // co-resident and could only flag a timeout after the fact - removed: nothing spins in this library.)
 #include "../../include/shadowkv_hip.h"
 #include "skv_common.h"
+#include "skv_fp8v.h"
 
 #define SKV_ROWS_PER_WG 8
 #define SKV_ROW_U128 128  // 16-byte units per chunk row
@@ -86,19 +87,27 @@ __global__ __launch_bounds__(256) void skv_stage_hits_kernel(MoveBuf b0, MoveBuf
     }
 }
 
-__global__ __launch_bounds__(256) void skv_land_rows_kernel(const u32x4* __restrict__ host_rows, u32x4* __restrict__ buf,
-                                                            const u32x4* __restrict__ temp,
-                                                            const int32_t* __restrict__ offsets,
-                                                            const int32_t* __restrict__ cnts, long long host_stride_u128,
-                                                            long long stride_u128, long long off_u128, int S) {
+// V8: the host table holds OCP e4m3fn bytes (1 KiB rows: the 8-byte unit `unit` of a row is the 16-byte unit `unit` of the
+// bf16 row) with one f32 scale per token row in v_scale [B][scale_stride]; only rows read from the
+// table are dequantised, moved hits are bf16 already.  The scale lookup goes out in front of the host load.
+template <bool V8>
+__device__ __forceinline__ void skv_land_rows_body(const void* __restrict__ host_rows, u32x4* __restrict__ buf,
+                                                   const u32x4* __restrict__ temp, const int32_t* __restrict__ offsets,
+                                                   const int32_t* __restrict__ cnts, long long host_stride_u128,
+                                                   long long stride_u128, long long off_u128, int S,
+                                                   const float* __restrict__ v_scale, long long scale_stride) {
     const int b = blockIdx.y, tid = threadIdx.x, unit = tid & 127, rsub = tid >> 7;
     const int cnt = cnts[b];
     u32x4 v[4];
     bool act[4];
+    u32x2 v8[4];
+    float sc[4];
+    bool deq[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int i = blockIdx.x * SKV_ROWS_PER_WG + k * 2 + rsub;
         act[k] = false;
+        deq[k] = false;
         if (i < S) {
             const int off = offsets[(size_t)b * S + i];
             if (i < cnt) {
@@ -108,15 +117,42 @@ __global__ __launch_bounds__(256) void skv_land_rows_kernel(const u32x4* __restr
                 }
             } else if (host_rows != nullptr) {
                 act[k] = true;
-                v[k] = host_rows[(long long)b * host_stride_u128 + (long long)off * SKV_ROW_U128 + unit];
+                if constexpr (V8) {
+                    deq[k] = true;
+                    sc[k] = v_scale[(long long)b * scale_stride + (long long)off * 8 + (unit >> 4)];
+                    v8[k] = reinterpret_cast<const u32x2*>(host_rows)[(long long)b * host_stride_u128 + (long long)off * SKV_ROW_U128 + unit];
+                } else {
+                    v[k] = reinterpret_cast<const u32x4*>(host_rows)[(long long)b * host_stride_u128 + (long long)off * SKV_ROW_U128 + unit];
+                }
             }
         }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int i = blockIdx.x * SKV_ROWS_PER_WG + k * 2 + rsub;
+        if constexpr (V8) {
+            if (deq[k]) v[k] = skv_e4m3x8_dequant(v8[k], sc[k]);
+        }
         if (act[k]) buf[(long long)b * stride_u128 + off_u128 + (long long)i * SKV_ROW_U128 + unit] = v[k];
     }
+}
+
+__global__ __launch_bounds__(256) void skv_land_rows_kernel(const u32x4* __restrict__ host_rows, u32x4* __restrict__ buf,
+                                                            const u32x4* __restrict__ temp,
+                                                            const int32_t* __restrict__ offsets,
+                                                            const int32_t* __restrict__ cnts, long long host_stride_u128,
+                                                            long long stride_u128, long long off_u128, int S) {
+    skv_land_rows_body<false>(host_rows, buf, temp, offsets, cnts, host_stride_u128, stride_u128, off_u128, S, nullptr, 0);
+}
+
+// host_stride_u64: 8-byte units between the (batch, head) blocks of the byte table
+__global__ __launch_bounds__(256) void skv_land_rows_fp8_kernel(const u32x2* __restrict__ host_rows, u32x4* __restrict__ buf,
+                                                                const u32x4* __restrict__ temp,
+                                                                const int32_t* __restrict__ offsets,
+                                                                const int32_t* __restrict__ cnts, long long host_stride_u64,
+                                                                long long stride_u128, long long off_u128, int S,
+                                                                const float* __restrict__ v_scale, long long scale_stride) {
+    skv_land_rows_body<true>(host_rows, buf, temp, offsets, cnts, host_stride_u64, stride_u128, off_u128, S, v_scale, scale_stride);
 }
 
 int skv_launch_stage_hits(void* k_buf, void* k_temp, void* v_buf, void* v_temp, const int32_t* offsets,
@@ -139,6 +175,19 @@ int skv_launch_land_rows(const void* host_rows, void* buf, const void* temp, con
     hipLaunchKernelGGL(skv_land_rows_kernel, dim3((S + SKV_ROWS_PER_WG - 1) / SKV_ROWS_PER_WG, B), dim3(256), 0, st,
                        (const u32x4*)host_rows, (u32x4*)buf, (const u32x4*)temp, offsets, cnts, host_len_elems / 8,
                        stride_elems / 8, off_elems / 8, S);
+    return SKV_OK;
+}
+
+// the FP8 table's landing: host_len_elems = bytes between the (batch, head) blocks of the table, scale_stride = f32 scales
+// (one per token row, 8 per chunk) between the blocks of v_scale
+int skv_launch_land_rows_fp8(const void* host_rows, const float* v_scale, void* buf, const void* temp, const int32_t* offsets,
+                             const int32_t* cnts, long long host_len_elems, long long scale_stride, long long stride_elems,
+                             long long off_elems, int B, int S, hipStream_t st) {
+    if (!host_rows || !v_scale || S < 1 || B < 1 || (host_len_elems % 16) || (scale_stride % 8) || (stride_elems % 8) || (off_elems % 8))
+        return SKV_ERR_ARG;
+    hipLaunchKernelGGL(skv_land_rows_fp8_kernel, dim3((S + SKV_ROWS_PER_WG - 1) / SKV_ROWS_PER_WG, B), dim3(256), 0, st,
+                       (const u32x2*)host_rows, (u32x4*)buf, (const u32x4*)temp, offsets, cnts, host_len_elems / 8,
+                       stride_elems / 8, off_elems / 8, S, v_scale, scale_stride);
     return SKV_OK;
 }
 

@@ -21,6 +21,7 @@
 // stored (they hold resident chunks).  The legacy entry point (pre-RoPE output buffer) shares the kernel.
 #include "skv_common.h"
 #include "skv_attn_body.h"
+#include "skv_fp8v.h"
 
 // Phase stamps for tools/rb_stamps.py (diagnostic build only, -DSKV_RB_STAMPS -> libshadowkv_hip_stamps.so; no stamp
 // executes in the shipped library).  100 MHz wall clock, one row of 8 per workgroup, a buffer nothing else reads.
@@ -71,6 +72,9 @@ struct AttnRole {
     const short* early_of;    // speculative early V fetch (skv_early.hip; null = off): staging index per chunk id
     const u32x4* early_staging;
     int early_chunks, early_max;
+    // FP8 V table (read by the MODE_V & 4 instantiations only): one f32 scale per token row
+    const float* v_scale;     // [bs*heads][v_scale_stride], 8 per chunk
+    long long v_scale_stride;
 };
 
 
@@ -201,7 +205,9 @@ __device__ __forceinline__ void skv_tile_pv_mfma(const unsigned char* s_v, const
     }
 }
 
-template <int MODE /*0 = pre-RoPE output, 1 = Llama RoPE, 2 = GLM RoPE*/, int KS, int AG = 0 /* attention role: G */>
+// MODE_V = MODE | 4 * V8.  V8: the landing role reads an FP8 (e4m3) V table; a bit of the first parameter rather than a
+// parameter of its own, so that the bf16 instantiations keep their names and their code.
+template <int MODE_V /* & 3: 0 = pre-RoPE output, 1 = Llama RoPE, 2 = GLM RoPE */, int KS, int AG = 0 /* attention role: G */>
 __global__ __launch_bounds__(AG > 0 ? 512 : 256, AG > 0 ? 2 : 1) void skv_rebuild_kernel(
     const bf16_t* __restrict__ U,        // [bs][seq_len][R]
     const bf16_t* __restrict__ SV,       // [bs][heads][128][R]
@@ -229,6 +235,9 @@ __global__ __launch_bounds__(AG > 0 ? 512 : 256, AG > 0 ? 2 : 1) void skv_rebuil
     // of LDS; __launch_bounds__(512, 2) = two waves per SIMD = that one workgroup), blocks get CUs in id order:
     // with all tiles first, a batch with more live tiles than CUs (bs >= 3 at 67 % hits) would start the attention blocks
     // only after the PCIe-bound tiles had drained and lose the overlap.
+    constexpr int MODE = MODE_V & 3;
+    constexpr bool V8 = (MODE_V & 4) != 0;
+    static_assert(!V8 || AG == 0, "the attention role lands bf16 rows");
     int bx = blockIdx.x, by = blockIdx.y;
     if constexpr (AG > 0) {
         const int per_head = rebuild_tiles + ar.splits;
@@ -270,6 +279,44 @@ __global__ __launch_bounds__(AG > 0 ? 512 : 256, AG > 0 ? 2 : 1) void skv_rebuil
             const int i = min(blk * 8 + k * 2 + rsub, S - 1);
             loffs[k] = hit_offsets[(size_t)bh2 * S + i];
             ldi[k] = dst_slots ? dst_slots[(size_t)bh2 * S + i] : i;
+        }
+        if constexpr (V8) {
+            // NOTE: this is a second copy of the landing loop below (lookups above shared; moved-hit load, selected-pointer
+            // load, store), kept apart so that the bf16 instantiations come out instruction for instruction as before.  A fix
+            // to one of the two loops belongs in the other as well.  (lv[] of the bf16 loop is not used here.)
+            // FP8 table: 1 KiB rows, thread `unit` reads the 8 bytes that become its 16-byte unit.  The scale of a miss row
+            // depends on the chunk id: it is looked up here, with the moved hits (bf16 rows of v_temp, HBM), in front of the
+            // host loads - loads return in order.  Rows that are not misses take scale word 0 / the dummy row and are not used.
+            float lsc[4];
+            u32x4 lh[4];
+            u32x2 l8[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = blk * 8 + k * 2 + rsub;
+                const bool moved_hit = i < S && i < cnt2 && !dst_slots && loffs[k] != i;
+                const bool miss = i < S && i >= cnt2;
+                lact[k] = moved_hit || miss;
+                lsc[k] = ar.v_scale[(long long)bh2 * ar.v_scale_stride + (miss ? (long long)loffs[k] * 8 + (unit >> 4) : 0)];
+                lh[k] = *(moved_hit ? v_temp + (((long long)bh2 * S + i) * 128 + unit)
+                                    : v_buf + ((long long)bh2 * v_stride_u128 + v_off_u128 + unit));
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = blk * 8 + k * 2 + rsub;
+                const bool miss = i < S && i >= cnt2;
+                const u32x2* src = miss ? reinterpret_cast<const u32x2*>(v_host) + ((long long)bh2 * v_host_stride_u128 + (long long)loffs[k] * 128 + unit)
+                                        : reinterpret_cast<const u32x2*>(v_buf + ((long long)bh2 * v_stride_u128 + v_off_u128)) + unit;
+                l8[k] = *src;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = blk * 8 + k * 2 + rsub;
+                const bool miss = i < S && i >= cnt2;
+                if (lact[k])
+                    v_buf[(long long)bh2 * v_stride_u128 + v_off_u128 + (long long)ldi[k] * 128 + unit] =
+                        miss ? skv_e4m3x8_dequant(l8[k], lsc[k]) : lh[k];
+            }
+            return;
         }
         // speculative early V fetch (skv_early.h): chunks already staged in HBM (one more dependent lookup, then no PCIe)
         int lsrc[4] = {-1, -1, -1, -1};
@@ -586,7 +633,8 @@ int skv_launch_rebuild(const void* U, const void* SV, const void* cos_sin, const
                        int C, long long cs_stride, long long out_stride_b, long long out_stride_h,
                        long long out_stride_s, int out_row0, int mode, const void* hit_temp, const int32_t* hit_offsets,
                        const int32_t* dst_slots, const void* v_host, void* v_buf, const void* v_temp, long long v_host_stride,
-                       long long v_stride, long long v_off, hipStream_t st, const AttnLaunch* attn, const EarlyConsume* early) {
+                       long long v_stride, long long v_off, hipStream_t st, const AttnLaunch* attn, const EarlyConsume* early,
+                       const float* v_scale, long long v_scale_stride) {
     if (head_dim != RB_D || C < 1 || S < 1) return SKV_ERR_UNSUPPORTED;
     if (R != 160 && R != 128 && R != 96 && R != 64) return SKV_ERR_UNSUPPORTED;  // instantiated ranks (LDS pitch fits <= 160)
     if ((out_stride_s % 8) || (out_stride_h % 8) || (out_stride_b % 8)) return SKV_ERR_ARG;
@@ -608,6 +656,12 @@ int skv_launch_rebuild(const void* U, const void* SV, const void* cos_sin, const
         ar.early_staging = (const u32x4*)early->early_staging;
         ar.early_chunks = early->early_chunks;
         ar.early_max = early->early_max;
+    }
+    if (v_scale) {                   // FP8 V table: the plain landing role only (no attention role, no early staging), rank 160
+        if (!v_buf || (v_host_stride % 16) || (v_scale_stride % 8)) return SKV_ERR_ARG;
+        if (attn || early || mode == 0 || R != 160) return SKV_ERR_UNSUPPORTED;
+        ar.v_scale = v_scale;
+        ar.v_scale_stride = v_scale_stride;
     }
     int attn_g = 0;
     size_t smem_all = smem;
@@ -672,7 +726,8 @@ int skv_launch_rebuild(const void* U, const void* SV, const void* cos_sin, const
         case 3: SKV_RB(M, 3); break; \
         default: SKV_RB(M, 2); break; \
     }
-    if (mode == 0) { SKV_RB_K(0) } else if (mode == 1) { SKV_RB_K(1) } else { SKV_RB_K(2) }
+    if (v_scale) { if (mode == 1) SKV_RB(1 | 4, 5); else SKV_RB(2 | 4, 5); }
+    else if (mode == 0) { SKV_RB_K(0) } else if (mode == 1) { SKV_RB_K(1) } else { SKV_RB_K(2) }
 #undef SKV_RB_K
 #undef SKV_RB
     return SKV_OK;

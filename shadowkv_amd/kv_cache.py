@@ -5,6 +5,7 @@ methods launch the hand-written gfx950 kernels of libshadowkv_hip.so.
 
 State (per layer l, batch b, KV head h; D = head_dim, C = chunk_size, S = sparse_budget // C):
   v_cache_cpu   pinned host  [L, bs, kv, max_length // C, C*D]   every V chunk, 2 KiB rows (C=8, D=128)
+        v_dtype="fp8_e4m3": float8_e4m3fn, 1 KiB rows, + v_scale f32 [L, bs, kv, max_length // C, C] in HBM (DESIGN.md section 11)
   k_/v_cache_buffer  HBM     [L, bs, kv, buf_len, D],  buf_len = R*C + 128 + (outlier + local)*C
         rows [0, prefill_local)            last tokens of the prompt (exact K / V)
         rows [prefill_local, sparse_start) outlier chunks (exact K / V)
@@ -55,7 +56,8 @@ def pinned_host_tensor(shape, dtype):
     as long as the cache, so it bypasses that allocator.  The memory is owned by the buffer object every view of the tensor
     keeps alive: it is freed when the LAST view (slices such as v_cache_cpu[l] included) is gone, not when the cache is.
     torch recognises the memory as pinned (is_pinned()), so GPU -> host copies into it are asynchronous DMA."""
-    nbytes = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
+    as_bytes = dtype == torch.float8_e4m3fn          # (the buffer protocol has no float8: bytes, viewed as float8)
+    nbytes = math.prod(shape) * (1 if as_bytes else torch.empty((), dtype=dtype).element_size())
     p = ctypes.c_void_p()
     rc = lib().skv_host_alloc(ctypes.byref(p), nbytes)
     if rc != 0 or not p.value:
@@ -63,6 +65,8 @@ def pinned_host_tensor(shape, dtype):
     buf = (ctypes.c_char * nbytes).from_address(p.value)
     fin = weakref.finalize(buf, lib().skv_host_free, p.value)
     fin.atexit = False      # at interpreter exit the HIP runtime may already be gone: the OS reclaims the pages
+    if as_bytes:
+        return torch.frombuffer(buf, dtype=torch.uint8).view(dtype).view(shape)
     return torch.frombuffer(buf, dtype=dtype).view(shape)
 
 
@@ -142,9 +146,16 @@ def gram_factorize(k, rank):
 
 class ShadowKVCache_CPU:
     def __init__(self, config, batch_size=1, max_length=32 * 1024, device="cuda:0", dtype=torch.bfloat16,
-                 sparse_budget=2048, chunk_size=8, rank=160, svd_mode="auto", v_offload=True, resident_sets=None):
+                 sparse_budget=2048, chunk_size=8, rank=160, svd_mode="auto", v_offload=True, resident_sets=None,
+                 v_dtype="bf16"):
         if dtype != torch.bfloat16:
             raise ValueError("ShadowKVCache_CPU supports bfloat16 only (as the reference's kernels do)")
+        if v_dtype not in tensor_op.V_DTYPES:           # (before anything is allocated)
+            raise ValueError(f"v_dtype must be one of {tensor_op.V_DTYPES}, got {v_dtype!r}")
+        # "fp8_e4m3" (DESIGN.md section 11): the chunked V table holds e4m3 bytes (1 KiB rows) with one f32 power-of-two scale
+        # per token row in HBM (v_scale) - half the PCIe bytes per miss and half the pinned memory.  Only the table is
+        # quantised; every V row of the sparse region equals dequant(table row of the chunk in that slot) at all times.
+        self.v_dtype = v_dtype
         self.config = config
         self.batch_size = batch_size
         self.max_length = max_length
@@ -190,12 +201,18 @@ class ShadowKVCache_CPU:
         # with v_offload=False, HBM (what the reference's GPU-resident ShadowKVCache does, kv_cache.py:155-506: the
         # same kernels then gather the misses at HBM speed; 8 GB per 122K-token sequence of the 288 GB)
         self.v_offload = bool(v_offload) or not on_gpu
+        fp8_v = v_dtype == "fp8_e4m3"
+        if fp8_v and (C != 8 or D != 128):
+            raise ValueError("v_dtype='fp8_e4m3' is built for chunk_size 8 and head_dim 128 (1 KiB table rows)")
+        table_shape, table_dtype = (L, bs, kv, max_length // C, D * C), (torch.float8_e4m3fn if fp8_v else dtype)
         if self.v_offload and on_gpu:
-            self.v_cache_cpu = pinned_host_tensor((L, bs, kv, max_length // C, D * C), dtype).zero_()
-        elif self.v_offload:
-            self.v_cache_cpu = torch.zeros(L, bs, kv, max_length // C, D * C, device="cpu", dtype=dtype)
+            self.v_cache_cpu = pinned_host_tensor(table_shape, table_dtype)
+            (self.v_cache_cpu.view(torch.uint8) if fp8_v else self.v_cache_cpu).zero_()
         else:
-            self.v_cache_cpu = torch.zeros(L, bs, kv, max_length // C, D * C, device=self.device, dtype=dtype)
+            table = torch.zeros(table_shape, device=self.device if on_gpu else "cpu", dtype=torch.uint8 if fp8_v else dtype)
+            self.v_cache_cpu = table.view(table_dtype) if fp8_v else table
+        # one scale per token row of the FP8 table; always on `device` (the scales never cross the host link)
+        self.v_scale = torch.ones(L, bs, kv, max_length // C, C, device=self.device, dtype=torch.float32) if fp8_v else None
         buf_len = self.resident_budget + 128 + (self.outlier_chunk + self.local_chunk) * C
         self.k_cache_buffer = torch.zeros(L, bs, kv, buf_len, D, device=self.device, dtype=dtype)
         self.v_cache_buffer = torch.zeros(L, bs, kv, buf_len, D, device=self.device, dtype=dtype)
@@ -397,8 +414,11 @@ class ShadowKVCache_CPU:
         self.prefill = incoming
         n_chunks_all = incoming // C
         self.max_ctx_chunks_len = n_chunks_all * C
-        self.v_cache_cpu[layer_idx][b0:b0 + bsz, :, :n_chunks_all].copy_(
-            new_v_cache[:, :, :self.max_ctx_chunks_len].reshape(bsz, kv, n_chunks_all, C * D), non_blocking=True)
+        if self.v_scale is not None:
+            self._fill_fp8_table(new_v_cache[:, :, :self.max_ctx_chunks_len], layer_idx, b0, n_chunks_all)
+        else:
+            self.v_cache_cpu[layer_idx][b0:b0 + bsz, :, :n_chunks_all].copy_(
+                new_v_cache[:, :, :self.max_ctx_chunks_len].reshape(bsz, kv, n_chunks_all, C * D), non_blocking=True)
 
         self.chunks = n_chunks_all - self.local_chunk
         self.chunks -= self.chunks % 8
@@ -442,7 +462,10 @@ class ShadowKVCache_CPU:
         tok = (chosen.unsqueeze(-1) * C + torch.arange(C, device=chosen.device)).view(bsz, kv, -1)
         tok = tok.unsqueeze(-1).expand(-1, -1, -1, D)
         sel_end = self.sparse_start + self.sparse_budget
-        vbuf[:, :, self.sparse_start:sel_end].copy_(new_v_cache.gather(-2, tok), non_blocking=True)
+        v_sel = new_v_cache.gather(-2, tok)
+        if self.v_scale is not None:     # the sparse region holds what a fetch of the same chunk would land: dequant(table row)
+            v_sel = self._fp8_round_trip(v_sel)
+        vbuf[:, :, self.sparse_start:sel_end].copy_(v_sel, non_blocking=True)
         kbuf[:, :, self.sparse_start:sel_end].copy_(key_states_roped.gather(-2, tok), non_blocking=True)
 
         if layer_idx == self.num_layers - 1:
@@ -453,9 +476,47 @@ class ShadowKVCache_CPU:
                 assert not torch.any(self.position_ids[..., :S] == -1), \
                     f"The cache for offloading is not built correctly, {self.position_ids}"
 
+    def _fill_fp8_table(self, v, layer_idx, b0, n_chunks):
+        """FP8 table rows and scales of the prompt's chunks: v bf16 [bsz, kv, n_chunks * C, D] (a strided view as it comes).  On
+        the GPU one native pass (skv_quantize_v_rows; the rows go straight into the table, pinned host memory included); on a
+        CPU device the torch mirror.  Same bytes either way."""
+        bsz = v.shape[0]
+        table = self.v_cache_cpu[layer_idx][b0:b0 + bsz, :, :n_chunks]
+        scale = self.v_scale[layer_idx][b0:b0 + bsz, :, :n_chunks]
+        if v.is_cuda:
+            tensor_op.quantize_v_rows(v, table, scale)      # (stream-ordered in front of every launch that reads the table)
+        else:
+            v8, sc = tensor_op.quantize_v_rows_torch(v)
+            table.view(torch.uint8).copy_(v8.view(torch.uint8).reshape(bsz, -1, n_chunks, self.chunk_size * self.head_dim))
+            scale.copy_(sc.view(bsz, -1, n_chunks, self.chunk_size))
+
+    def _fp8_round_trip(self, rows):
+        """dequant(quant(rows)) of bf16 token rows [bsz, kv, n, D], by the same quantiser that fills the table."""
+        if rows.is_cuda:
+            bsz, kv, n, D = rows.shape
+            v8 = torch.empty(bsz, kv, n * D, dtype=torch.uint8, device=rows.device)
+            sc = torch.empty(bsz, kv, n, dtype=torch.float32, device=rows.device)
+            tensor_op.quantize_v_rows(rows, v8, sc)
+            return tensor_op.dequantize_v_rows(v8.view(torch.float8_e4m3fn).view(bsz, kv, n, D), sc)
+        return tensor_op.dequantize_v_rows(*tensor_op.quantize_v_rows_torch(rows))
+
+    def _refuse_fp8_v(self, what, why):
+        if self.v_scale is not None:
+            raise RuntimeError(f"{what} is not available with v_dtype='fp8_e4m3': {why}")
+
+    def _land_v(self, lv, what):
+        """The V landing launch of the reference layout (moved hits from the staging buffer, misses from the table)."""
+        vhost, vbuf = lv.vhost, lv.vbuf
+        args = (ptr(vhost), ptr(vbuf), ptr(self._temp_v), ptr(self.offsets), ptr(self.cnts), vhost.stride(1), vbuf.stride(1),
+                self.sparse_start * self.head_dim, self.block_num, self.select_sets)
+        if self.v_scale is not None:
+            check(lib().skv_land_chunks_fp8(*args, ptr(lv.vscale), lv.vscale.stride(1), current_stream_handle()), what)
+        else:
+            check(lib().skv_land_chunks(*args, current_stream_handle()), what)
+
     # ------------------------------------------------------------------ decode (native)
     class _LayerViews:
-        __slots__ = ("kbuf", "vbuf", "vhost", "lm", "lm_idx", "pos", "U", "SV", "cnts", "age")
+        __slots__ = ("kbuf", "vbuf", "vhost", "vscale", "lm", "lm_idx", "pos", "U", "SV", "cnts", "age")
 
     def _layer(self, l):
         """Per-layer views of the state tensors, built once (indexing a tensor makes a new view object every time: ~2 us
@@ -470,6 +531,7 @@ class ShadowKVCache_CPU:
                 v.kbuf, v.vbuf, v.vhost = self.k_cache_buffer[i], self.v_cache_buffer[i], self.v_cache_cpu[i]
                 v.lm, v.lm_idx, v.pos = self.k_landmark[i], self.k_landmark_idx[i], self.position_ids[i]
                 v.U, v.SV, v.cnts, v.age = self.U[i], self.SV[i], self._cnts_layers[i], self._slot_age[i]
+                v.vscale = None if self.v_scale is None else self.v_scale[i]
                 self._lv.append(v)
             self._lv_key = key
         return self._lv[l]
@@ -592,14 +654,12 @@ class ShadowKVCache_CPU:
         if not self.inplace_methods:
             self._reference_layout_only("get_value_cache")
         lv = self._layer(layer_idx)
-        vhost, vbuf = lv.vhost, lv.vbuf
+        vbuf = lv.vbuf
         self._flush_pending_v()
         if self.lazy_value_fetch:
             self._pending_v = (layer_idx, position_ids)
             return vbuf[:, :, :self.sparse_end + self._gen_rows(layer_idx)]
-        check(lib().skv_land_chunks(ptr(vhost), ptr(vbuf), ptr(self._temp_v), ptr(self.offsets), ptr(self.cnts),
-                                    vhost.stride(1), vbuf.stride(1), self.sparse_start * self.head_dim,
-                                    self.block_num, self.select_sets, current_stream_handle()), "get_value_cache")
+        self._land_v(lv, "get_value_cache")
         return vbuf[:, :, :self.sparse_end + self._gen_rows(layer_idx)]
 
     def get_key_cache(self, layer_idx, position_ids, rope_func, cos_sin_cache):
@@ -638,6 +698,7 @@ class ShadowKVCache_CPU:
             self.sum = torch.zeros(bs * kv, G, (n + 255) // 256, device=self.device, dtype=torch.float32)
 
     def _ref_guard(self, what):
+        self._refuse_fp8_v(f"{what} with reference_calls=True", "the reference's twelve-name API moves bf16 rows")
         if self.resident_sets != self.select_sets or self.inplace_methods or self.lazy_value_fetch:
             raise RuntimeError(f"{what}: reference_calls reproduces the reference's launch sequence, which has neither a larger "
                                "resident set nor the in-place / deferred variants")
@@ -696,10 +757,7 @@ class ShadowKVCache_CPU:
                 raise RuntimeError("inplace_methods: a deferred get_value_cache needs a get_key_cache call to carry it out")
             self._fetch_inplace(layer_idx, self._last_cos_sin)
             return
-        lv = self._layer(layer_idx)
-        check(lib().skv_land_chunks(ptr(lv.vhost), ptr(lv.vbuf), ptr(self._temp_v), ptr(self.offsets), ptr(self.cnts),
-                                    lv.vhost.stride(1), lv.vbuf.stride(1), self.sparse_start * self.head_dim,
-                                    self.block_num, self.select_sets, current_stream_handle()), "get_value_cache (deferred)")
+        self._land_v(self._layer(layer_idx), "get_value_cache (deferred)")
 
     def fetch_kv(self, layer_idx, position_ids, cos_sin_cache):
         """get_value_cache + get_key_cache of one layer as a single launch on the current stream (K rebuild
@@ -720,6 +778,9 @@ class ShadowKVCache_CPU:
             self._early_pub = None
             check(lib().skv_fetch_kv_early(*args, ptr(ea["states"][layer_idx]), self.num_key_value_groups, ea["n_lm"],
                                            ea["n_chunks"], ea["E"], current_stream_handle()), "fetch_kv (early)")
+        elif self.v_scale is not None:
+            vs = self.v_scale[layer_idx]
+            check(lib().skv_fetch_kv_fp8(*args, ptr(vs), vs.stride(1), current_stream_handle()), "fetch_kv (fp8 V)")
         else:
             check(lib().skv_fetch_kv(*args, current_stream_handle()), "fetch_kv")
 
@@ -763,6 +824,9 @@ class ShadowKVCache_CPU:
         if ea is not None:
             check(L.skv_fetch_kv_inplace_early(*fetch_args, ptr(ea["states"][layer_idx]), self.num_key_value_groups, ea["n_lm"],
                                                ea["n_chunks"], ea["E"], st), "fetch_kv_inplace_early")
+        elif self.v_scale is not None:
+            vs = self.v_scale[layer_idx]
+            check(L.skv_fetch_kv_inplace_fp8(*fetch_args, ptr(vs), vs.stride(1), st), "fetch_kv_inplace (fp8 V)")
         else:
             check(L.skv_fetch_kv_inplace(*fetch_args, st), "fetch_kv_inplace")
         self._fetch_event(ev0, layer_idx)
@@ -796,14 +860,15 @@ class ShadowKVCache_CPU:
         # Batches are PCIe-bound outright and keep the link busier with the plain fetch launch (separate landing
         # workgroups, two per CU) + the standalone attention: measured 296 / 451 / 596 / 739 tok/s at bs 2 / 4 / 8 / 24
         # against 292 / 427 / 562 / 687 with the fused launch
+        # (an FP8 V table: the fused launch's landing waves read bf16 rows - the plain launch dequantises)
         return (self.rank == 160 and self.chunk_size == 8 and self.head_dim == 128 and self.select_sets % 8 == 0
                 and self.num_key_value_groups in (4, 8) and self.OVERLAP_SPLITS + self.select_sets // 8 <= 128
-                and self.block_num <= 8)
+                and self.block_num <= 8 and self.v_scale is None)
 
     def early_fetch_supported(self):
         """Shapes the early-fetch roles are built for (csrc/skv_early.h): <= 65,536 landmarks and <= 1,024 resident slots per
-        head, V table in pinned host memory."""
-        return (self.k_landmark is not None and self.k_landmark.shape[-2] <= 65536 and self.resident_sets <= 1024
+        head, V table in pinned host memory, bf16 (the staging buffer and the roles that fill and read it move 2 KiB rows)."""
+        return (self.v_scale is None and self.k_landmark is not None and self.k_landmark.shape[-2] <= 65536 and self.resident_sets <= 1024
                 and self.v_cache_cpu is not None and self.v_cache_cpu.is_pinned())
 
     def _early_state(self):
@@ -852,6 +917,7 @@ class ShadowKVCache_CPU:
             self._early = None
             self._early_request = None
             return
+        self._refuse_fp8_v("enable_early_fetch", "the early and near staging roles move 2 KiB bf16 rows")
         if not self.early_fetch_supported():
             raise RuntimeError("early fetch needs the prefilled state with the V table in pinned host memory, at most 65,536 "
                                "landmarks and at most 1,024 resident slots per head")
@@ -963,6 +1029,8 @@ class ShadowKVCache_CPU:
         like tensor_op.sparse_attention_decode; same values up to the order of the f32 sums.
         kv_proj (tensor_op.norm_q_rope): the new token's K / V row is still to be computed - a role of the selection
         launches does it before the fetch launch attends the generated rows."""
+        self._refuse_fp8_v("select_fetch_attend_inplace", "the fused launch's landing waves read bf16 rows "
+                                                          "(can_overlap_attention() is False: use select_fetch_inplace)")
         if query_states.shape[-2] != 1:
             raise ValueError("decode-time selection expects q_len == 1")
         buf_rows = self.k_cache_buffer.shape[-2]

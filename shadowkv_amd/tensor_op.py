@@ -64,6 +64,49 @@ def dequantize_fp8_rows(w8, scale, dtype=torch.bfloat16):
     return (w8.float() * scale.float().unsqueeze(1)).to(dtype)
 
 
+# ---------------------------------------------------------------------------- FP8 V offload table
+V_DTYPES = ("bf16", "fp8_e4m3")
+V_SCALE_MIN_EXP, V_SCALE_MAX_EXP = -100, 100
+
+
+def quantize_v_rows_torch(v):
+    """Torch mirror of skv_quantize_v_rows (any device): v [..., D] -> (e4m3fn bytes [..., D], f32 scale [...]) per token row:
+    scale = the smallest power of two with max|v| / scale <= 448, clamped to [2^-100, 2^100], 1 for an all-zero row;
+    byte = e4m3fn(RNE(clamp(v / scale, -448, 448))).  Rows with NaN / Inf are outside the contract."""
+    vf = v.float()
+    amax = vf.abs().amax(dim=-1)
+    m, e = torch.frexp(amax)                               # amax = m * 2^e, m in [0.5, 1); 448 = 0.875 * 2^9
+    k = torch.where(m <= 0.875, e - 9, e - 8).clamp(V_SCALE_MIN_EXP, V_SCALE_MAX_EXP)
+    k = torch.where(amax > 0, k, torch.zeros_like(k))
+    one = torch.ones_like(amax)
+    scale, inv = torch.ldexp(one, k), torch.ldexp(one, -k)
+    v8 = (vf * inv.unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return v8, scale
+
+
+def dequantize_v_rows(v8, scale, dtype=torch.bfloat16):
+    """scale * e4m3(byte) per token row: v8 [..., D] float8_e4m3fn, scale [...] f32.  The product is a bf16 number (exact)."""
+    return (v8.float() * scale.unsqueeze(-1)).to(dtype)
+
+
+def quantize_v_rows(v, table, scale):
+    """skv_quantize_v_rows: v bf16 [bs, kv, T, 128] (any strides with a contiguous last dimension - the transposed view of a
+    fused QKV output is taken as it is, nothing is copied) -> table [bs, kv, >= T * 128] bytes / float8 and scale
+    [bs, kv, >= T] f32, both views whose (batch, head) blocks are evenly spaced and whose rows are contiguous."""
+    bs, kv, T, D = v.shape
+    tb, sb = table.reshape(bs, kv, -1) if table.dim() != 3 else table, scale.reshape(bs, kv, -1) if scale.dim() != 3 else scale
+    if tb.data_ptr() != table.data_ptr() or sb.data_ptr() != scale.data_ptr():
+        raise ValueError("table / scale must be views with contiguous rows per (batch, head)")
+    if v.dtype != torch.bfloat16 or v.stride(3) != 1 or tb.element_size() != 1 or sb.dtype != torch.float32:
+        raise ValueError("quantize_v_rows takes bf16 rows, a byte table and f32 scales")
+    if tb.stride(2) != 1 or sb.stride(2) != 1 or (bs > 1 and (tb.stride(0) != kv * tb.stride(1) or sb.stride(0) != kv * sb.stride(1))):
+        raise ValueError("table / scale blocks must be evenly spaced over (batch, head)")
+    if tb.shape[2] < T * D or sb.shape[2] < T:
+        raise ValueError("table / scale rows are shorter than the token rows to quantise")
+    check(lib().skv_quantize_v_rows(ptr(v), v.stride(0), v.stride(1), v.stride(2), bs, kv, T, D, ptr(tb), tb.stride(1),
+                                    ptr(sb), sb.stride(1), current_stream_handle()), "quantize_v_rows")
+
+
 def _fp8_check(w, w_scale):
     if w.dtype != torch.float8_e4m3fn:
         raise ValueError("w_scale goes with float8_e4m3fn weights")
