@@ -28,7 +28,10 @@ def _case(blocks, chunks, seed, extra_rows=0):
     return k
 
 
-@pytest.mark.parametrize("blocks,chunks,extra", [(1, 1, 0), (3, 5, 0), (8, 1021, 0), (2, 4100, 40), (16, 257, 8)])
+@pytest.mark.parametrize("blocks,chunks,extra", [(1, 1, 0), (3, 5, 0), (8, 1021, 0), (2, 4100, 40), (16, 257, 8),
+                                                 # the grid is capped at 4,096 workgroups x 4 chunks: past 16,384 chunks the
+                                                 # grid-stride loop repeats (bench.py's 200 K / 244 K contexts: 25,600 / 31,232)
+                                                 (2, 16389, 8)])
 def test_chunk_stats_bit_exact_against_oracle(blocks, chunks, extra):
     from shadowkv_amd import tensor_op
     k = _case(blocks, chunks, 11 * blocks + chunks, extra)                            # [blocks, rows, 128]

@@ -456,8 +456,8 @@ def test_norm_gemv_statistics_see_every_element():
         assert_norm(y[:K], dr.rmsnorm_ref(href, w, 1e-5)[perm], f"norm gemv spike at {sp[i]}")
 
 
-@pytest.mark.parametrize("rows", [1, 3])
-@pytest.mark.parametrize("I", [8, 1000, 13696, 14336])
+# (300 x 14336: 537,600 vectors of 8 - the grid is capped at 2,048 workgroups x 256 vectors, so the grid-stride loop repeats)
+@pytest.mark.parametrize("I,rows", [(I, rows) for rows in (1, 3) for I in (8, 1000, 13696, 14336)] + [(14336, 300)])
 def test_silu_and_mul(I, rows):
     _lib, L, st = _L()
     g = torch.Generator().manual_seed(I + rows)

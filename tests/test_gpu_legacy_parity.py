@@ -242,6 +242,65 @@ def test_rope_new_and_v1(sk):
     assert_bits_equal(o0, o2, "apply_rotary_pos_emb (separate tables)")
 
 
+# The grid of skv_rope_kernel is capped at 4,096 workgroups x 256 threads, one 8-element unit each (8 units per row, 16 for GLM): a
+# launch with more than 1,048,576 units goes round the grid-stride loop more than once (the prefill of a 122 K prompt: ~30 times).
+# 4 heads x 32,800 rows x 8 = 2 heads x 32,800 rows x 16 = 1,049,600 units: the second round holds the last 1,024.
+LOOP_ROWS = 32800
+
+
+def test_rope_new_v1_and_v2_beyond_one_grid_round(sk):
+    g = torch.Generator().manual_seed(19)
+    bs, heads, s, L, C = 1, 4, LOOP_ROWS, 40000, 8
+    assert bs * heads * s * 8 > 4096 * 256
+    x = torch.randn(bs, heads, s, 128, generator=g).bfloat16()
+    cs = _cos_sin(L, 128, g)
+    ids = torch.stack([torch.randperm(L // C, generator=g)[:s // C] for _ in range(bs * heads)]).view(bs, heads, s // C).to(torch.int32)
+    pid = (ids.to(torch.int64).unsqueeze(-1) * C + torch.arange(C)).view(bs, heads, s).contiguous()   # v2's positions, per token
+    o0 = torch.zeros_like(x)
+    ints = (bs, heads, s, 128, x.stride(0), x.stride(1), x.stride(2), x.stride(3), cs.stride(0), pid.stride(0),
+            pid.stride(1), pid.stride(2), 64)
+    oracle.apply_rotary_pos_emb_new(x, cs, pid, o0, *ints)
+    xd, csd, pidd = x.to(DEV), cs.to(DEV), pid.to(DEV)
+    o1 = torch.zeros_like(x, device=DEV)
+    sk.apply_rotary_pos_emb_new(xd, csd, pidd, o1, *ints)
+    cosf = torch.cat((cs[:, :64], cs[:, :64]), -1).contiguous(); sinf = torch.cat((cs[:, 64:], cs[:, 64:]), -1).contiguous()
+    o2 = torch.zeros_like(x, device=DEV)
+    sk.apply_rotary_pos_emb(xd, cosf.to(DEV), sinf.to(DEV), pidd, o2, bs, heads, s, 128, x.stride(0), x.stride(1), x.stride(2),
+                            x.stride(3), 128, 128, pid.stride(0), pid.stride(1), pid.stride(2), 64)
+    o3 = torch.zeros_like(x, device=DEV)
+    sk.apply_rotary_pos_emb_new_v2(xd, csd, ids.to(DEV), o3, bs, heads, s, 128, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                                   cs.stride(0), ids.stride(0), ids.stride(1), ids.stride(2), 64, C)
+    torch.cuda.synchronize()
+    assert_bits_equal(o0, o1, "apply_rotary_pos_emb_new")
+    assert_bits_equal(o0, o2, "apply_rotary_pos_emb (separate tables)")
+    assert_bits_equal(o0, o3, "apply_rotary_pos_emb_new_v2")
+
+
+@pytest.mark.parametrize("glm", [False, True])
+def test_rope_push_cache_beyond_one_grid_round(sk, glm):
+    g = torch.Generator().manual_seed(23 + glm)
+    bs, heads, C, L = 1, 2 if glm else 4, 8, 40000
+    S = LOOP_ROWS // C
+    assert bs * heads * S * C * (16 if glm else 8) > 4096 * 256
+    x = torch.randn(bs, heads, S * C, 128, generator=g).bfloat16()
+    cs = _cos_sin(L, 64 if glm else 128, g)
+    ids = torch.stack([torch.randperm(L // C, generator=g)[:S] for _ in range(bs * heads)]).view(bs, heads, S).to(torch.int32)
+    cnts = torch.randint(0, 64, (bs * heads,), generator=g, dtype=torch.int32)      # the rows of the last round are all live
+    cnts[0] = 0
+    buf_rows, start = 64 + S * C + 16, 64
+    cache0 = torch.randn(bs, heads, buf_rows, 128, generator=g).bfloat16()
+    cache1 = cache0.to(DEV)
+    ints = (bs, heads, S * C, 128, x.stride(0), x.stride(1), x.stride(2), x.stride(3), cs.stride(0),
+            ids.stride(0), ids.stride(1), ids.stride(2), cache0.stride(0), cache0.stride(1), cache0.stride(2),
+            start, start + S * C, 64, C)
+    fn0 = oracle.apply_rotary_pos_emb_push_cache_opt_glm if glm else oracle.apply_rotary_pos_emb_push_cache_opt
+    fn1 = sk.apply_rotary_pos_emb_push_cache_opt_glm if glm else sk.apply_rotary_pos_emb_push_cache_opt
+    fn0(x, cs, ids, cache0, cnts, *ints)
+    fn1(x.to(DEV), cs.to(DEV), ids.to(DEV), cache1, cnts.to(DEV), *ints)
+    torch.cuda.synchronize()
+    assert_bits_equal(cache0, cache1, "key cache after RoPE push")
+
+
 def test_unsupported_shapes_raise(sk):
     from shadowkv_amd._lib import ShadowKVNativeError
     z = torch.zeros(8, dtype=torch.int64, device=DEV)
