@@ -705,6 +705,39 @@ SKV_EXPORT int skv_fetch_kv_inplace_fp8(const void* U, const void* SV, const voi
                              long long cache_stride_s, int sparse_start, int rope_mode, long long host_block_stride,
                              const float* v_scale, long long scale_block_stride, skv_stream_t stream);
 
+/* ---- part 8: weight-only MXFP4 (e2m1 + e8m0 block scales) decode GEMVs --------------------------- */
+
+/* The one-token projections of part 7 with the weight matrix in the OCP MX FP4 format: W4 [N][K / 2] bytes row-major - element
+ * 2i of a row in the low nibble of byte i, element 2i + 1 in the high nibble (torch.float4_e2m1fn_x2 order); a nibble is a sign
+ * bit and an e2m1 code with the values {0, 0.5, 1, 1.5, 2, 3, 4, 6} - and scale_e8m0 [N][K / 32] bytes row-major, one per 32
+ * consecutive elements of a row:  W[n][k] = 2^(scale_e8m0[n][k / 32] - 127) * e2m1(nibble[n][k]).  x, bias, y and every other
+ * operand stay bf16.  Per output row t = sum_k f32(2^s(n, k / 32) * e2m1(n, k)) * f32(x[k]): the block scale is applied to the
+ * weight (exact), f32 accumulation, no multiply after the reduction; t then takes exactly the epilogue of the bf16 entry of the
+ * same name.  h_out of the norm variants is bit-identical to skv_add_rmsnorm's.  The contract is stated for scale bytes
+ * 27..227 (2^-100 .. 2^100).
+ * K % 32 == 0 and K >= 1024 (the norm variants: K == 4096), W4 16-byte aligned; anything else: SKV_ERR_UNSUPPORTED.  A null
+ * W4 / scale_e8m0 / x / y or N < 1: SKV_ERR_ARG.  Every argument check runs on the host before any HIP call and returns what
+ * the FP8 entry of the same name returns for the same mistake.  The remaining arguments are those of the FP8 entries. */
+SKV_EXPORT int skv_gemv_mxfp4(const void* W4, const void* scale_e8m0, const void* x, const void* bias, void* y, int N, int K,
+                 int fuse_silu_mul, skv_stream_t stream);
+SKV_EXPORT int skv_norm_gemv_mxfp4(const void* W4, const void* scale_e8m0, const void* x, const void* residual, const void* norm_weight,
+                      float eps, void* h_out, const void* bias, void* y, int N, int K, int fuse_silu_mul, skv_stream_t stream);
+SKV_EXPORT int skv_norm_gemv_rangemax_mxfp4(const void* W4, const void* scale_e8m0, const void* x, const void* residual,
+                               const void* norm_weight, float eps, void* h_out, const void* bias, void* y, int N, int K,
+                               void* range_max, skv_stream_t stream);
+SKV_EXPORT int skv_qkv_gemv_rope_update_mxfp4(const void* Wqkv4, const void* scale_e8m0, const void* x, const void* residual,
+                                 const void* norm_weight, float eps, void* h_out, const void* bias, const void* cos_sin,
+                                 const int64_t* pos, const int64_t* row_idx, const void* q_override, void* q_out, void* k_cache,
+                                 void* v_cache, int K, int q_heads, int kv_heads, int head_dim, long long cos_sin_stride,
+                                 int cos_sin_rows, long long cache_stride_h, int cache_rows, int rope_mode, skv_stream_t stream);
+SKV_EXPORT int skv_norm_gemv_near_pull_mxfp4(const void* W4, const void* scale_e8m0, const void* x, const void* residual,
+                                const void* norm_weight, float eps, void* h_out, void* y, int N, int K, void* early_state,
+                                int blocks, int groups, int n_landmarks, int n_chunks, int early_max, const void* v_host,
+                                long long host_block_stride, int pull_parts, int active_lists, skv_stream_t stream);
+SKV_EXPORT int skv_gemv_near_pull_mxfp4(const void* W4, const void* scale_e8m0, const void* x, const void* bias, void* y, int N, int K,
+                           void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
+                           const void* v_host, long long host_block_stride, int pull_parts, int list, skv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,13 @@ _SIGS = {
     "skv_qkv_gemv_rope_update_fp8": (c_int, [c_p] * 5 + [c_f] + [c_p] * 9 + [c_int] * 4 + [c_ll, c_int, c_ll] + [c_int] * 2 + [c_p]),
     "skv_norm_gemv_near_pull_fp8": (c_int, [c_p] * 5 + [c_f] + [c_p] * 2 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
     "skv_gemv_near_pull_fp8": (c_int, [c_p] * 5 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
+    # weight-only MXFP4 (e2m1 nibbles + e8m0 block scales): the FP8 signatures with the scale bytes behind the weights
+    "skv_gemv_mxfp4": (c_int, [c_p] * 5 + [c_int] * 3 + [c_p]),
+    "skv_norm_gemv_mxfp4": (c_int, [c_p] * 5 + [c_f] + [c_p] * 3 + [c_int] * 3 + [c_p]),
+    "skv_norm_gemv_rangemax_mxfp4": (c_int, [c_p] * 5 + [c_f] + [c_p] * 3 + [c_int] * 2 + [c_p, c_p]),
+    "skv_qkv_gemv_rope_update_mxfp4": (c_int, [c_p] * 5 + [c_f] + [c_p] * 9 + [c_int] * 4 + [c_ll, c_int, c_ll] + [c_int] * 2 + [c_p]),
+    "skv_norm_gemv_near_pull_mxfp4": (c_int, [c_p] * 5 + [c_f] + [c_p] * 2 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
+    "skv_gemv_near_pull_mxfp4": (c_int, [c_p] * 5 + [c_int] * 2 + [c_p] + [c_int] * 5 + [c_p, c_ll, c_int, c_int, c_p]),
     # FP8 (e4m3) V offload table: the bf16 entries with (v_scale, scale_block_stride) in front of the stream
     "skv_quantize_v_rows": (c_int, [c_p] + [c_ll] * 3 + [c_int] * 4 + [c_p, c_ll, c_p, c_ll, c_p]),
     "skv_land_chunks_fp8": (c_int, [c_p] * 5 + [c_ll] * 3 + [c_int] * 2 + [c_p, c_ll, c_p]),

@@ -71,16 +71,24 @@ class DecoderLayer:
         self.post_attention_layernorm_weight = torch.ones(h, device=device, dtype=dtype)
         self.input_layernorm_variance_epsilon = cfg.rms_norm_eps
         self.post_attention_layernorm_variance_epsilon = cfg.rms_norm_eps
-        # f32 row scales of the four matrices once DecoderLM.quantize_weights has made them float8_e4m3fn; None: bf16 weights
+        # f32 row scales of the four matrices once DecoderLM.quantize_weights has made them float8_e4m3fn (or their e8m0 block
+        # scale bytes once it has made them MXFP4 nibbles); None: bf16 weights
         self.wqkv_scale = self.wo_scale = self.gate_up_proj_scale = self.down_proj_scale = None
 
     MATRICES = ("wqkv", "wo", "gate_up_proj", "down_proj")
 
     def prefill_weight(self, name):
-        """The matrix as the prefill GEMMs read it: itself (bf16), or a bf16 temporary dequantised from FP8 - one elementwise
-        torch op, freed by the caller's scope."""
-        w, sc = getattr(self, name), getattr(self, name + "_scale")
-        return w if sc is None else tensor_op.dequantize_fp8_rows(w, sc, torch.bfloat16)
+        """The matrix as the prefill GEMMs read it: itself (bf16), or a bf16 temporary dequantised from FP8 / MXFP4 - elementwise
+        torch ops, freed by the caller's scope."""
+        return _dequantized(getattr(self, name), getattr(self, name + "_scale"))
+
+
+def _dequantized(w, sc):
+    if sc is None:
+        return w
+    if w.dtype == torch.uint8:
+        return tensor_op.dequantize_mxfp4_rows(w, sc, torch.bfloat16)
+    return tensor_op.dequantize_fp8_rows(w, sc, torch.bfloat16)
 
 
 def build_cos_sin_cache(cfg, max_pos, device, dtype):
@@ -117,7 +125,9 @@ def load_minference_pattern(pattern, num_layers, num_heads):
     return out
 
 
-WEIGHT_DTYPES = ("bf16", "fp8_e4m3")     # "fp8_e4m3": weight-only FP8, per-row f32 scales
+# "fp8_e4m3": weight-only FP8, per-row f32 scales; "mxfp4": weight-only MXFP4, e2m1 nibbles with one e8m0
+# scale byte per 32 elements of a row
+WEIGHT_DTYPES = ("bf16", "fp8_e4m3", "mxfp4")
 
 
 class DecoderLM:
@@ -205,27 +215,38 @@ class DecoderLM:
         self._last_range_max = None     # the keys of the logits forward_fused returned last (None: not produced)
         self.lm_head_scale = None       # f32 [vocab] once the lm_head is FP8
         self.weight_dtype = "bf16"
-        if weight_dtype == "fp8_e4m3":  # random bf16 init, then quantised: the same seed gives the bf16 model's weights, quantised
-            self.quantize_weights()
+        if weight_dtype != "bf16":      # random bf16 init, then quantised: the same seed gives the bf16 model's weights, quantised
+            self.quantize_weights(dtype=weight_dtype)
 
-    def quantize_weights(self, pow2_scale=False):
-        """Weight-only FP8 in place: wqkv, wo, gate_up_proj, down_proj of every layer and the lm_head become float8_e4m3fn with
-        one f32 scale per output row (`<name>_scale`, tensor_op.quantize_fp8_rows); embed_tokens, the norm weights and the biases
-        stay bf16.  Idempotent: a model that is already FP8 is left as it is."""
-        if self.weight_dtype == "fp8_e4m3":
+    def quantize_weights(self, pow2_scale=False, dtype="fp8_e4m3"):
+        """Weight-only quantisation in place: wqkv, wo, gate_up_proj, down_proj of every layer and the lm_head become
+        "fp8_e4m3": float8_e4m3fn with one f32 scale per output row (`<name>_scale`, tensor_op.quantize_fp8_rows), or
+        "mxfp4": packed e2m1 nibbles uint8 [N, K / 2] with the e8m0 block scale bytes uint8 [N, K / 32] in `<name>_scale`
+        (tensor_op.quantize_mxfp4_rows; pow2_scale is not read).
+        embed_tokens, the norm weights and the biases stay bf16.  Idempotent: a model that already has the format is left as it
+        is; a model quantised to the other format is refused (ValueError)."""
+        if dtype not in WEIGHT_DTYPES or dtype == "bf16":
+            raise ValueError(f"quantize_weights takes dtype 'fp8_e4m3' or 'mxfp4', got {dtype!r}")
+        if self.weight_dtype == dtype:
             return self
+        if self.weight_dtype != "bf16":
+            raise ValueError(f"the model's weights are {self.weight_dtype} already: quantise a bf16 model to {dtype}")
+
+        def quantize(w):
+            return tensor_op.quantize_mxfp4_rows(w) if dtype == "mxfp4" else tensor_op.quantize_fp8_rows(w, pow2_scale=pow2_scale)
+
         for layer in self.layers:
             for name in DecoderLayer.MATRICES:
-                w8, sc = tensor_op.quantize_fp8_rows(getattr(layer, name), pow2_scale=pow2_scale)
-                setattr(layer, name, w8)
+                wq, sc = quantize(getattr(layer, name))
+                setattr(layer, name, wq)
                 setattr(layer, name + "_scale", sc)
-        self.lm_head, self.lm_head_scale = tensor_op.quantize_fp8_rows(self.lm_head, pow2_scale=pow2_scale)
-        self.weight_dtype = "fp8_e4m3"
+        self.lm_head, self.lm_head_scale = quantize(self.lm_head)
+        self.weight_dtype = dtype
         return self
 
     def weight_bytes(self):
         """Bytes of the matrices a decode step streams (one embedding row is read per token: not counted); FP8 matrices count
-        their bytes plus 4 per row for the scales."""
+        their bytes plus 4 per row for the scales, MXFP4 matrices N K / 2 nibble bytes plus N K / 32 scale bytes."""
         def nbytes(w, sc):
             return w.numel() * w.element_size() + (0 if sc is None else sc.numel() * sc.element_size())
 
@@ -235,7 +256,7 @@ class DecoderLM:
         return n
 
     def _lm_head_prefill(self):
-        return self.lm_head if self.lm_head_scale is None else tensor_op.dequantize_fp8_rows(self.lm_head, self.lm_head_scale)
+        return _dequantized(self.lm_head, self.lm_head_scale)
 
     # --------------------------------------------------------------- per-layer pieces (llama.py:283-427)
     def _decode_scratch(self, bs):

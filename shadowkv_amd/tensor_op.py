@@ -107,6 +107,137 @@ def quantize_v_rows(v, table, scale):
                                     ptr(sb), sb.stride(1), current_stream_handle()), "quantize_v_rows")
 
 
+# ---------------------------------------------------------------------------- weight-only MXFP4
+MXFP4_BLOCK = 32                                   # elements that share one e8m0 scale byte (OCP MX)
+MXFP4_MIN_K = 1024                                 # smallest K of the native GEMV
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)     # e2m1 codes 0..7; bit 3 of a nibble is the sign
+
+
+def quantize_mxfp4_rows(w):
+    """(w4, w_scale): w [N, K], K % 32 == 0 -> uint8 [N, K / 2] (element 2i in the low nibble of byte i, element 2i + 1 in the
+    high nibble; nibble = sign bit + e2m1 code) and uint8 e8m0 scales [N, K / 32], one per 32 consecutive elements of a row:
+    w[n][k] ~ 2^(w_scale[n][k / 32] - 127) * e2m1(nibble[n][k]).  Per block the scale is the smallest power of two 2^s with
+    max|w| / 2^s <= 6 (frexp, as quantize_v_rows_torch: nothing is ever clipped), s clamped to [-100, 100] (bytes 27..227; an
+    all-zero block: s = 0); elements are w / 2^s rounded to the nearest e2m1 value, ties to the even mantissa.  Rows with
+    NaN / Inf are outside the contract.  Torch ops only, any device."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4_rows takes a [N, K] matrix with K % {MXFP4_BLOCK} == 0")
+    N, K = w.shape
+    wf = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=-1)
+    m, e = torch.frexp(amax)                               # amax = m * 2^e, m in [0.5, 1); 6 = 0.75 * 2^3
+    s = torch.where(m <= 0.75, e - 3, e - 2).clamp(V_SCALE_MIN_EXP, V_SCALE_MAX_EXP)
+    s = torch.where(amax > 0, s, torch.zeros_like(s))
+    inv = ((127 - s).to(torch.int32) << 23).view(torch.float32)     # 2^-s from its bits: exact on every device
+    a = wf.abs() * inv.unsqueeze(-1)                      # (a block whose max is below 2^-100's reach rounds towards 0)
+    # nearest e2m1 value, ties to the even mantissa: the grid step is 0.5 below 2, 1 in [2, 4), 2 in [4, 6]; torch.round is RNE
+    # and the even multiples of each step are the codes with mantissa bit 0
+    q = torch.where(a < 2, torch.round(a * 2) * 0.5, torch.where(a < 4, torch.round(a), torch.round(a * 0.5) * 2)).clamp_max(6.0)
+    code = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q * 0.5 + 4)).to(torch.uint8)
+    nib = (code | ((wf < 0).to(torch.uint8) << 3)).reshape(N, K // 2, 2)
+    w4 = nib[..., 0] | (nib[..., 1] << 4)
+    return w4.contiguous(), (s + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4_rows(w4, w_scale, dtype=torch.bfloat16):
+    """2^(w_scale - 127) * e2m1(nibble) as `dtype` [N, K]: what prefill, the MXFP4 fallbacks and the tests use.  Every value has
+    2 significant bits: exact in bf16 for scale bytes 27..227."""
+    _mxfp4_check(w4, w_scale)
+    N = w4.shape[0]
+    nib = torch.stack((w4 & 0xF, w4 >> 4), dim=-1).reshape(N, -1).long()
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=w4.device)[nib & 7]
+    val = torch.where((nib & 8) != 0, -mag, mag).reshape(N, -1, MXFP4_BLOCK)
+    scale = (w_scale.to(torch.int32) << 23).view(torch.float32)     # 2^(byte - 127) from its bits
+    return (val * scale.unsqueeze(-1)).reshape(N, -1).to(dtype)
+
+
+def _mxfp4_check(w, w_scale):
+    if w.dtype != torch.uint8 or w.dim() != 2:
+        raise ValueError("MXFP4 weights are a uint8 [N, K / 2] tensor of packed e2m1 nibbles")
+    N, K = w.shape[0], 2 * w.shape[1]
+    if K % MXFP4_BLOCK or w_scale is None or w_scale.dtype != torch.uint8 or tuple(w_scale.shape) != (N, K // MXFP4_BLOCK):
+        raise ValueError(f"MXFP4 weights uint8 [N, K / 2] = {tuple(w.shape)} go with e8m0 scales uint8 [N, K / 32] = "
+                         f"({N}, {K // MXFP4_BLOCK}) with K % 32 == 0, got "
+                         f"{None if w_scale is None else (w_scale.dtype, tuple(w_scale.shape))}")
+
+
+def _mxfp4_check_x(x, w, w_scale):
+    _mxfp4_check(w, w_scale)
+    if x.shape[-1] != 2 * w.shape[1]:
+        raise ValueError(f"x [..., K] with K = {x.shape[-1]} does not match MXFP4 weights uint8 [N, K / 2] = {tuple(w.shape)} "
+                         f"and scales uint8 [N, K / 32]")
+
+
+def _mxfp4_native(x, w, w_scale, rows):
+    """Shapes the MXFP4 GEMV kernels take: one token row, K % 32 == 0, K >= 1024, contiguous operands."""
+    K = x.shape[-1]
+    return rows == 1 and K % MXFP4_BLOCK == 0 and K >= MXFP4_MIN_K and x.is_contiguous() and w.is_contiguous() and w_scale.is_contiguous()
+
+
+mxfp4_native_calls = 0    # native MXFP4 launches / dequantising fallbacks taken so far (diagnostics; the tests read them)
+mxfp4_fallback_calls = 0
+
+
+def _mxfp4_linear_fallback(x, w, w_scale, bias, fuse_silu_mul):
+    """CORRECT AND SLOW: the weights are dequantised to a bf16 temporary on every call, then F.linear (more than one token row,
+    K < 1024, non-contiguous operands)."""
+    global mxfp4_fallback_calls
+    mxfp4_fallback_calls += 1
+    out = F.linear(x, dequantize_mxfp4_rows(w, w_scale, x.dtype), bias)
+    return silu_and_mul_fused(out) if fuse_silu_mul else out
+
+
+def _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows):
+    global mxfp4_native_calls
+    _mxfp4_check_x(x, w, w_scale)
+    N = w.shape[0]
+    native = _mxfp4_native(x, w, w_scale, rows)
+    if near_pull is not None:
+        if not native or fuse_silu_mul or N > 8192:
+            raise ValueError("near_pull rides in a one-token GEMV launch with at most 8,192 output rows")
+        y = out if out is not None else torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
+        check(lib().skv_gemv_near_pull_mxfp4(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, *near_pull,
+                                             current_stream_handle()), "gemv_near_pull_mxfp4")
+        mxfp4_native_calls += 1
+        return y
+    if not native:
+        y = _mxfp4_linear_fallback(x, w, w_scale, bias, fuse_silu_mul)
+        return y if out is None else out.copy_(y)
+    y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
+    check(lib().skv_gemv_mxfp4(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0,
+                               current_stream_handle()), "gemv_mxfp4")
+    mxfp4_native_calls += 1
+    return y
+
+
+def _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull):
+    global mxfp4_native_calls
+    _mxfp4_check_x(x, w, w_scale)
+    K, N = x.shape[-1], w.shape[0]
+    one_launch = x.numel() == K == 4096 and x.is_contiguous() and w.is_contiguous() and w_scale.is_contiguous()
+    if near_pull is not None and (not one_launch or not fuse_silu_mul or bias is not None or range_max is not None):
+        raise ValueError("near_pull rides in the one-token gate/up launch (hidden size 4096, fused SiLU * mul, no bias)")
+    if range_max is not None and (not one_launch or fuse_silu_mul or not range_max_supported(x.numel(), K, N)):
+        raise ValueError("range_max: one token, hidden size 4096, N % 16 == 0, N <= 262,144, no fused SiLU")
+    if not one_launch:
+        h, hs = add_rmsnorm(x, residual, norm_w, eps)
+        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale)
+    y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
+    h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
+    head = (ptr(w), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0)
+    if near_pull is not None:
+        check(lib().skv_norm_gemv_near_pull_mxfp4(*head, ptr(y), N, K, *near_pull, current_stream_handle()),
+              "norm_gemv_near_pull_mxfp4")
+    elif range_max is not None:
+        check(lib().skv_norm_gemv_rangemax_mxfp4(*head, ptr(bias), ptr(y), N, K, ptr(range_max), current_stream_handle()),
+              "norm_gemv_rangemax_mxfp4")
+    else:
+        check(lib().skv_norm_gemv_mxfp4(*head, ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0, current_stream_handle()),
+              "norm_gemv_mxfp4")
+    mxfp4_native_calls += 1
+    return h, y
+
+
 def _fp8_check(w, w_scale):
     if w.dtype != torch.float8_e4m3fn:
         raise ValueError("w_scale goes with float8_e4m3fn weights")
@@ -159,10 +290,15 @@ def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None
     K < 1024 or non-contiguous operands fall back to F.linear over the dequantised weights (correct, slow).
     fp8_rows ("fallback" | "native"; read with w_scale only): "native" sends 2..MAX_GEMV_ROWS contiguous token rows with
     K % 64 == 0 through skv_linear_rows_fp8 - the FP8 bytes stream once, nothing is dequantised; every
-    other multi-row shape still falls back.  One token row, near_pull and the default are unchanged."""
+    other multi-row shape still falls back.  One token row, near_pull and the default are unchanged.
+    w uint8 [N, K / 2] with w_scale uint8 [N, K / 32] (quantize_mxfp4_rows): an MXFP4 pair - one contiguous token row with
+    K % 32 == 0 and K >= 1024 takes the native MXFP4 GEMV (near_pull included), everything else the dequantising fallback;
+    fp8_rows is not read."""
     _fp8_rows_check(fp8_rows)
     K = x.shape[-1]
     rows = x.numel() // K
+    if w.dtype == torch.uint8:          # an MXFP4 pair (fp8_rows does not apply to it)
+        return _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows)
     if w_scale is not None:
         return _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, fp8_rows)
     if near_pull is not None:
@@ -231,10 +367,13 @@ def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=Fal
     near_pull (gate/up launch of a ShadowKV layer only; ShadowKVCache_CPU.near_pull_args(layer)): the launch's first workgroups
     stage the near misses of this step's selection ahead of the next step (skv_norm_gemv_near_pull_bf16); same y.
     w_scale (f32 [N]): w holds float8_e4m3fn bytes - the same one-launch paths with the FP8 kernels (same h, bit for bit);
-    other shapes: add_rmsnorm + linear_decode(..., w_scale=, fp8_rows=) - fp8_rows as in linear_decode."""
+    other shapes: add_rmsnorm + linear_decode(..., w_scale=, fp8_rows=) - fp8_rows as in linear_decode.
+    An MXFP4 pair (w uint8 [N, K / 2], w_scale uint8 [N, K / 32]) takes the same paths with the MXFP4 kernels."""
     _fp8_rows_check(fp8_rows)
     K = x.shape[-1]
     N = w.shape[0]
+    if w.dtype == torch.uint8:          # an MXFP4 pair (fp8_rows does not apply to it)
+        return _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull)
     if w_scale is not None:
         return _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
                                        fp8_rows)
@@ -338,18 +477,32 @@ def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row
     rotated k and v are pushed into row row_idx of k_cache / v_cache [1, Hkv, rows, D].  One native launch when the
     hidden size is 4096 and bs == 1; otherwise norm_linear_decode + qkv_rope_update.
     w_scale (f32 [rows of wqkv]): wqkv holds float8_e4m3fn bytes - the same two paths with the FP8 kernels; fp8_rows as in
-    linear_decode (the multi-row path's projection)."""
-    global fp8_native_calls
+    linear_decode (the multi-row path's projection).  An MXFP4 pair (wqkv uint8 [N, K / 2], w_scale uint8 [N, K / 32]) takes
+    the same two paths with the MXFP4 kernels."""
+    global fp8_native_calls, mxfp4_native_calls
     _fp8_rows_check(fp8_rows)
     K = x.shape[-1]
     D = k_cache.shape[-1]
-    if w_scale is not None:
+    mx = wqkv.dtype == torch.uint8
+    if mx:
+        _mxfp4_check_x(x, wqkv, w_scale)
+    elif w_scale is not None:
         _fp8_check(wqkv, w_scale)
-    if x.numel() != K or K != 4096 or not x.is_contiguous() or not wqkv.is_contiguous() or D != 128:
+    if x.numel() != K or K != 4096 or not x.is_contiguous() or not wqkv.is_contiguous() or D != 128 \
+            or (mx and not w_scale.is_contiguous()):
         h, qkv = norm_linear_decode(x, residual, norm_w, eps, wqkv, bqkv, w_scale=w_scale, fp8_rows=fp8_rows)
         return h, qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_heads, q_override)
     q = torch.empty(1, q_heads, 1, D, dtype=x.dtype, device=x.device)
     h = torch.empty_like(x) if residual is not None else x
+    if mx:
+        check(lib().skv_qkv_gemv_rope_update_mxfp4(ptr(wqkv), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps),
+                                                   ptr(h) if residual is not None else 0, ptr(bqkv), ptr(cos_sin), ptr(pos),
+                                                   ptr(row_idx), ptr(q_override), ptr(q), ptr(k_cache), ptr(v_cache), K, q_heads,
+                                                   kv_heads, D, cos_sin.stride(0), cos_sin.shape[0], k_cache.stride(1),
+                                                   k_cache.shape[2], 1 if cos_sin.shape[-1] == 128 else 2, current_stream_handle()),
+              "qkv_gemv_rope_update_mxfp4")
+        mxfp4_native_calls += 1
+        return h, q
     if w_scale is not None:
         check(lib().skv_qkv_gemv_rope_update_fp8(ptr(wqkv), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps),
                                                  ptr(h) if residual is not None else 0, ptr(bqkv), ptr(cos_sin), ptr(pos),
@@ -370,7 +523,7 @@ def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row
 
 def kv_proj_split_supported(x, wqkv, k_cache):
     """Shapes norm_q_rope + the k/v role take: one token of one sequence, hidden size 4096, head_dim 128, bf16 weights (the
-    k/v role reads bf16 rows: FP8 models use the one QKV launch)."""
+    k/v role reads bf16 rows: FP8 and MXFP4 models use the one QKV launch)."""
     K = x.shape[-1]
     return bool(wqkv.dtype == torch.bfloat16 and x.is_cuda and x.numel() == K == 4096 and x.is_contiguous() and wqkv.is_contiguous() and k_cache.shape[-1] == 128
                 and k_cache.shape[0] == 1)
@@ -384,6 +537,8 @@ def norm_q_rope(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row_idx, k_c
     other arguments must stay alive and unchanged until that call."""
     if wqkv.dtype == torch.float8_e4m3fn:
         raise ValueError("the q / kv split of the QKV projection reads bf16 weight rows: FP8 weights take norm_qkv_rope_update")
+    if wqkv.dtype == torch.uint8:
+        raise ValueError("the q / kv split of the QKV projection reads bf16 weight rows: MXFP4 weights take norm_qkv_rope_update")
     if not kv_proj_split_supported(x, wqkv, k_cache):
         raise ValueError("the q / kv split of the QKV projection takes one token of one sequence, hidden size 4096, head_dim 128")
     K, D = x.shape[-1], 128

@@ -2,7 +2,10 @@
 """tokens/s of the headline configuration (Llama-3.1-8B shapes, 122 K synthetic context, budget 2048, hipGraph, in-place
 layout with overlap_attention, bs 1) with bf16 weights and with weight-only FP8 weights, on one box in one process: the bf16
 model is built and timed, then quantised in place (DecoderLM.quantize_weights) and timed again over the SAME context and
-query walk.  usage: tools/fp8_e2e.py [--steps K] [--warmup W] [--layers L] [--batch B] [--out FILE]   (FILE is appended to)
+query walk.  usage: tools/fp8_e2e.py [--steps K] [--warmup W] [--layers L] [--batch B] [--weight-dtype D] [--out FILE]
+(FILE is appended to).  --weight-dtype {fp8_e4m3,mxfp4} (bs 1): the format the second measurement quantises to (default
+fp8_e4m3); given explicitly it also appends the relative deviation of one probe step's logits from the bf16 model's (same
+token, same synthetic queries, same context - a random-weight figure, not an accuracy measurement).
 --batch B (B > 1): the batched headline configuration (in-place layout, V in pinned host memory, eager decode_step - a captured
 graph at bs > 1 is not part of the FP8 rows work) as a triple over one context, measured one after the other: the bf16 model, the
 FP8 model with the dequantising fallback, the FP8 model with fp8_rows="native" (skv_linear_rows_fp8)."""
@@ -32,6 +35,18 @@ def run(model, ctx, steps, warmup, seed=4242):
         dec.step()[:, -1].tolist()                      # per-step host sync, as the benchmark
     torch.cuda.synchronize()
     return steps / (time.perf_counter() - t0)
+
+
+def probe_logits(model, ctx, seed=77):
+    """The logits of ONE fused decode step right after the prefill state: a fixed token, a fixed synthetic query table."""
+    c = model.kv_cache
+    c.kv_offset, c.gen_offset = ctx, 0
+    table = llama.make_walk_table(model, 1, step=0.3, seed=seed)
+    tok = torch.tensor([[17]], device=model.device)
+    row = c.sparse_end + c.gen_offset
+    lg = model.forward_fused(tok, model.get_ctx(tok), torch.tensor([row], device=model.device), kv_len=row + 1, q_table=table[0])
+    torch.cuda.synchronize()
+    return lg[:, -1].float().clone()
 
 
 def run_eager(model, ctx, steps, warmup, seed=4242):
@@ -88,7 +103,11 @@ def main():
     ap.add_argument("--layers", type=int, default=None)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--weight-dtype", dest="weight_dtype", choices=("fp8_e4m3", "mxfp4"), default=None)
     a = ap.parse_args()
+    wd = a.weight_dtype or "fp8_e4m3"
+    if a.batch > 1 and wd != "fp8_e4m3":
+        ap.error("--batch > 1 measures the FP8 rows paths: --weight-dtype applies to bs 1")
     if a.batch > 1:
         lines = batched(a)
         print("\n".join(lines))
@@ -105,15 +124,20 @@ def main():
     model.kv_cache.enable_early_fetch(near=True)        # the headline's default for G <= 4
     res = {}
     res["bf16"] = (run(model, ctx, a.steps, a.warmup), model.weight_bytes(), model.kv_proj_split_launches > 0)
-    model.quantize_weights()
+    ref = probe_logits(model, ctx) if a.weight_dtype else None
+    model.quantize_weights(dtype=wd)
     torch.cuda.empty_cache()
-    res["fp8_e4m3"] = (run(model, ctx, a.steps, a.warmup), model.weight_bytes(), False)
+    res[wd] = (run(model, ctx, a.steps, a.warmup), model.weight_bytes(), False)
     lines = [f"# tools/fp8_e2e.py on {torch.cuda.get_device_name(0)}: 122 K synthetic context, budget 2048, hipGraph, in-place + "
              f"overlap_attention, bs 1, {model.num_layers} layers, {a.steps} steps after {a.warmup} warm-up steps"]
     for k, (tps, nbytes, split) in res.items():
         lines.append(f"weight_dtype {k:<9} {tps:8.2f} tokens/s  {1e6 / tps / model.num_layers:7.2f} us/layer  weights {nbytes / 1e9:6.2f} GB"
                      f"  qkv {'split (q launch + k/v role)' if split else 'one launch'}")
-    lines.append(f"fp8 : bf16 tokens/s ratio {res['fp8_e4m3'][0] / res['bf16'][0]:.3f}")
+    lines.append(f"{'fp8' if wd == 'fp8_e4m3' else wd} : bf16 tokens/s ratio {res[wd][0] / res['bf16'][0]:.3f}")
+    if ref is not None:
+        got = probe_logits(model, ctx)
+        lines.append(f"probe step (token 17, fixed synthetic queries): |logits_{wd} - logits_bf16| / |logits_bf16| = "
+                     f"{float((got - ref).norm() / ref.norm()):.3e}  (random weights: not an accuracy measurement)")
     print("\n".join(lines))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -7,12 +7,9 @@ from shadowkv_amd import tensor_op, llama
 dev = "cuda:0"
 
 
-def fp8_mode(out_path=None, rounds=7, reps=24):
-    """--fp8 [FILE]: every FP8 launch against the bf16 launch of the same shape (skv_gemv.hip, unchanged), HBM-cold.
-    Per shape three captured graphs of `reps` iterations: [flush], [flush, FP8 launch], [flush, bf16 launch] - the flush
-    rewrites a 1 GiB buffer (four times L2 + the 256 MiB last-level cache), so every launch reads its weights from HBM.  The
-    graphs are replayed in interleaved rounds; a launch's time is (its graph - the flush graph) / reps within the round, the
-    reported figure the median over the rounds.  bytes: the weights (+ 4 N of scales); the activations are noise next to them."""
+def _fixture(reps):
+    """The five launches of a decode step's dense half (fn(w, w_scale): bf16 with None, FP8 or MXFP4 by the pair), the graph
+    builder and the timer that --fp8 and --mxfp4 share: (g, shapes, graph_of, timed)."""
     torch.manual_seed(0)
     g = torch.Generator(device=dev).manual_seed(0)
     flush = torch.zeros(1 << 30, dtype=torch.uint8, device=dev)
@@ -24,10 +21,6 @@ def fp8_mode(out_path=None, rounds=7, reps=24):
     pos = torch.tensor([[100]], device=dev); row = torch.tensor([5], device=dev)
     kc = torch.zeros(1, 8, 64, 128, device=dev, dtype=torch.bfloat16); vc = torch.zeros_like(kc)
     rm = torch.zeros(1, 128256 // 16, dtype=torch.int16, device=dev)
-
-    def weights(n, k):
-        w = (torch.randn(n, k, device=dev, generator=g) * 0.02).bfloat16()
-        return (w,) + tensor_op.quantize_fp8_rows(w)
 
     shapes = [
         ("qkv 6144x4096 (norm+rope+push)", 6144, 4096,
@@ -61,6 +54,21 @@ def fp8_mode(out_path=None, rounds=7, reps=24):
         e0.record(); gr.replay(); e1.record(); torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / reps           # us per iteration
 
+    return g, shapes, graph_of, timed
+
+
+def fp8_mode(out_path=None, rounds=7, reps=24):
+    """--fp8 [FILE]: every FP8 launch against the bf16 launch of the same shape (skv_gemv.hip, unchanged), HBM-cold.
+    Per shape three captured graphs of `reps` iterations: [flush], [flush, FP8 launch], [flush, bf16 launch] - the flush
+    rewrites a 1 GiB buffer (four times L2 + the 256 MiB last-level cache), so every launch reads its weights from HBM.  The
+    graphs are replayed in interleaved rounds; a launch's time is (its graph - the flush graph) / reps within the round, the
+    reported figure the median over the rounds.  bytes: the weights (+ 4 N of scales); the activations are noise next to them."""
+    g, shapes, graph_of, timed = _fixture(reps)
+
+    def weights(n, k):
+        w = (torch.randn(n, k, device=dev, generator=g) * 0.02).bfloat16()
+        return (w,) + tensor_op.quantize_fp8_rows(w)
+
     lines = [f"# tools/time_gemv.py --fp8 on {torch.cuda.get_device_name(0)}: HBM-cold launches (1 GiB flush before each), "
              f"median of {rounds} interleaved rounds of {reps} launches; us per launch, TB/s over the weight bytes",
              f"{'shape':<34} {'fp8 us':>8} {'TB/s':>6} {'bf16 us':>8} {'TB/s':>6} {'bf16/fp8':>9} {'flush us':>9}"]
@@ -88,9 +96,54 @@ def fp8_mode(out_path=None, rounds=7, reps=24):
             f.write("\n".join(lines) + "\n")
 
 
+def mxfp4_mode(out_path=None, rounds=7, reps=24):
+    """--mxfp4 [FILE]: the method of --fp8 with three launches per shape - bf16, FP8 and MXFP4 - in interleaved rounds of one
+    process: per shape four captured graphs of `reps` iterations ([flush], [flush, launch] per format), a launch's time is
+    (its graph - the flush graph) / reps within the round, the reported figure the median over the rounds.  bytes: the weights
+    (+ 4 N of FP8 row scales; + N K / 32 of MXFP4 block scales).  Acceptance: no MXFP4 launch slower than the FP8 launch of
+    the same shape; the margin is the spread (max - min) of that FP8 launch's rounds."""
+    g, shapes, graph_of, timed = _fixture(reps)
+    lines = [f"# tools/time_gemv.py --mxfp4 on {torch.cuda.get_device_name(0)}: HBM-cold launches (1 GiB flush before each), "
+             f"median of {rounds} interleaved rounds of {reps} launches; us per launch, TB/s over the weight bytes",
+             f"{'shape':<34} {'bf16 us':>8} {'TB/s':>6} {'fp8 us':>8} {'TB/s':>6} {'mxfp4 us':>9} {'TB/s':>6} {'fp8 spread':>11} "
+             f"{'bf16/mx':>8} {'fp8/mx':>7}  verdict"]
+    med = lambda v: sorted(v)[len(v) // 2]
+    slower = []
+    for name, n, k, fn in shapes:
+        wb = (torch.randn(n, k, device=dev, generator=g) * 0.02).bfloat16()
+        w8, s8 = tensor_op.quantize_fp8_rows(wb)
+        w4, s4 = tensor_op.quantize_mxfp4_rows(wb)
+        g0, gb = graph_of(None), graph_of(lambda: fn(wb, None))
+        g8, g4 = graph_of(lambda: fn(w8, s8)), graph_of(lambda: fn(w4, s4))
+        tb, t8, t4 = [], [], []
+        for _ in range(rounds):
+            f = timed(g0); b = timed(gb); a = timed(g8); c = timed(g4)
+            tb.append(b - f); t8.append(a - f); t4.append(c - f)
+        ub, u8, u4, spread = med(tb), med(t8), med(t4), max(t8) - min(t8)
+        bb, b8, b4 = 2 * n * k, n * k + 4 * n, n * k // 2 + n * k // 32
+        ok = u4 <= u8 + spread
+        if not ok:
+            slower.append(name)
+        lines.append(f"{name:<34} {ub:8.2f} {bb / ub * 1e-6:6.2f} {u8:8.2f} {b8 / u8 * 1e-6:6.2f} {u4:9.2f} {b4 / u4 * 1e-6:6.2f} "
+                     f"{spread:11.2f} {ub / u4:8.2f} {u8 / u4:7.2f}  {'no slower than FP8' if ok else 'SLOWER THAN FP8'}")
+        print(lines[-1], flush=True)
+        del wb, w8, s8, w4, s4, g0, gb, g8, g4
+    lines.append("# " + ("every MXFP4 launch is no slower than the FP8 launch of its shape" if not slower else
+                         "MXFP4 LAUNCHES SLOWER THAN FP8 beyond the FP8 rounds' spread: " + "; ".join(slower)))
+    print(lines[-1])
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if "--fp8" in sys.argv:
     i = sys.argv.index("--fp8")
     fp8_mode(sys.argv[i + 1] if len(sys.argv) > i + 1 else None)
+    sys.exit(0)
+if "--mxfp4" in sys.argv:
+    i = sys.argv.index("--mxfp4")
+    mxfp4_mode(sys.argv[i + 1] if len(sys.argv) > i + 1 else None)
     sys.exit(0)
 L = 32
 g = torch.Generator(device=dev).manual_seed(0)
