@@ -6,7 +6,8 @@
 // by scale[n]; t then takes exactly the epilogue of skv_linear_rows_bf16.  Activations stay bf16: e4m3 -> bf16 is exact, the
 // multiply is v_mfma_f32_16x16x32_bf16.
 //
-// Structure, tile shapes and the (SILU_PAIR, MT, RT, NWV) family are those of skv_rows_gemm.hip; only the weight operand changes.
+// Tile shapes, the (SILU_PAIR, MT, RT, NWV) family, the reduction, the epilogue and the host's branch tree are skv_rows_frame.h,
+// shared with skv_rows_gemm.hip; this file keeps the weight operand's stream.
 // A 16-byte load now holds 16 weights, so a k-step is 64 elements and feeds TWO MFMAs:
 //     A operand (weights): lane (a = lane & 15, g = lane >> 4) loads 16 B = W8[row a][64 s + 16 g .. +16]  (nontemporal);
 //                          bytes 0..7 -> 8 bf16 for the first MFMA, bytes 8..15 for the second (4 + 4 v_cvt_scalef32_pk_bf16_fp8,
@@ -17,10 +18,7 @@
 //     D                  : lane holds D[rows 4 g .. 4 g + 3][token a]
 // Per 16 B of weights: 8 conversions and 2 * MT MFMAs.
 #include "../../include/shadowkv_hip.h"
-#include "skv_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "skv_rows_frame.h"
 
 #ifndef RG8_WAVES
 #define RG8_WAVES 8
@@ -52,30 +50,18 @@ __global__ __launch_bounds__(RG8_WAVES * 64) void skv_rows_gemm_fp8_kernel(const
                                                                            const bf16_t* __restrict__ bias, bf16_t* __restrict__ Y,
                                                                            int N, int K, int M, int I /* SILU_PAIR: rows of one half */) {
     static_assert(!(PAIRX && MT > 1), "the paired token operand serves one tile of <= 8 tokens");
-    __shared__ float s_red[RG8_WAVES][MT][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int a = lane & 15, g = lane >> 4;
-    int row;
-    if (SILU_PAIR) {  // tile = 8 gate rows (a < 8) + the matching 8 up rows
-        int idx = blockIdx.x * 8 + (a & 7);
-        if (idx >= I) idx = I - 1;  // clamp: computed and discarded
-        row = a < 8 ? idx : I + idx;
-    } else {
-        row = blockIdx.x * 16 + a;
-        if (row >= N) row = N - 1;
-    }
-    const uint8_t* wp = W + (size_t)row * K + 16 * g;
-    const int tokl = PAIRX ? (a & 7) : a;
+    const int a = skv_rows_a(lane), g = skv_rows_g(lane);
+    const uint8_t* wp = W + skv_rows_weight_row<SILU_PAIR>(blockIdx.x, a, N, I) * K + 16 * g;
     const bf16_t* xp[MT];                                               // batches (PAIRX: lanes a >= 8 at the second vector)
     const bf16_t* xs[MT];                                               // single steps: every lane both vectors of its token
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
-        const int tok = min(16 * t + tokl, M - 1);                       // columns >= M: a duplicate, never stored
-        xs[t] = X + (size_t)tok * K + 16 * g;
+        xs[t] = X + (size_t)skv_rows_token(t, PAIRX ? (a & 7) : a, M) * K + 16 * g;
         xp[t] = xs[t] + (PAIRX ? (a >> 3) * 8 : 0);
     }
-    const int S = K / 64, per = (S + RG8_WAVES - 1) / RG8_WAVES;
-    const int s0 = wave * per, s1 = min(S, s0 + per);
+    int s0, s1;
+    skv_rows_k_slice<RG8_WAVES>(K / 64, wave, s0, s1);
     f32x4 acc0[MT], acc1[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
@@ -130,35 +116,12 @@ __global__ __launch_bounds__(RG8_WAVES * 64) void skv_rows_gemm_fp8_kernel(const
             acc1[t] = mfma_bf16(w1, xv[t][1], acc1[t]);
         }
     }
+    f32x4 acc[1][MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) s_red[wave][t][4 * g + r][a] = acc0[t][r] + acc1[t][r];
-    __syncthreads();
-    if (SILU_PAIR) {
-        if (tid < 8 * M) {
-            const int tok = tid >> 3, i = tid & 7, idx = blockIdx.x * 8 + i;
-            if (idx < I) {
-                float gs = 0.f, us = 0.f;
-#pragma unroll
-                for (int w = 0; w < RG8_WAVES; ++w) {
-                    gs += s_red[w][tok >> 4][i][tok & 15];
-                    us += s_red[w][tok >> 4][i + 8][tok & 15];
-                }
-                const float gg = bfr(scale[idx] * gs), uu = bfr(scale[I + idx] * us);  // the projection outputs are bf16 tensors
-                Y[(size_t)tok * I + idx] = f2bf(bfr(gg / (1.0f + __expf(-gg))) * uu);
-            }
-        }
-    } else if (tid < 16 * M) {
-        const int tok = tid >> 4, r = tid & 15, n = blockIdx.x * 16 + r;
-        if (n < N) {
-            float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < RG8_WAVES; ++w) t += s_red[w][tok >> 4][r][tok & 15];
-            t *= scale[n];                       // the row's scale: one f32 multiply after the reduction
-            Y[(size_t)tok * N + n] = f2bf(bias ? bfr(t) + bf2f(bias[n]) : t);
-        }
-    }
+        for (int r = 0; r < 4; ++r) acc[0][t][r] = acc0[t][r] + acc1[t][r];
+    skv_rows_epilogue<SILU_PAIR, true, true, RG8_WAVES>(acc, tid, a, g, scale, bias, Y, N, M, I);
 }
 
 // Second generation (skv_rows_gemm2_kernel): a wave walks RT tiles of 16 weight rows over its K slice, so one token-operand load
@@ -168,28 +131,16 @@ __global__ __launch_bounds__(NWV * 64) void skv_rows_gemm2_fp8_kernel(const uint
                                                                       const bf16_t* __restrict__ X, const bf16_t* __restrict__ bias,
                                                                       bf16_t* __restrict__ Y, int N, int K, int M,
                                                                       int I /* SILU_PAIR: rows of one half */) {
-    __shared__ float s_red[NWV][MT][RT][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int a = lane & 15, g = lane >> 4;
+    const int a = skv_rows_a(lane), g = skv_rows_g(lane);
     const uint8_t* wp[RT];
 #pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        int row;
-        if (SILU_PAIR) {  // tile = 8 gate rows (a < 8) + the matching 8 up rows
-            int idx = (blockIdx.x * RT + r) * 8 + (a & 7);
-            if (idx >= I) idx = I - 1;  // clamp: computed and discarded
-            row = a < 8 ? idx : I + idx;
-        } else {
-            row = (blockIdx.x * RT + r) * 16 + a;
-            if (row >= N) row = N - 1;
-        }
-        wp[r] = W + (size_t)row * K + 16 * g;
-    }
+    for (int r = 0; r < RT; ++r) wp[r] = W + skv_rows_weight_row<SILU_PAIR>(blockIdx.x * RT + r, a, N, I) * K + 16 * g;
     const bf16_t* xs[MT];
 #pragma unroll
-    for (int t = 0; t < MT; ++t) xs[t] = X + (size_t)min(16 * t + a, M - 1) * K + 16 * g;   // columns >= M: a duplicate, never stored
-    const int S = K / 64, per = (S + NWV - 1) / NWV;
-    const int s0 = wave * per, s1 = min(S, s0 + per);
+    for (int t = 0; t < MT; ++t) xs[t] = X + (size_t)skv_rows_token(t, a, M) * K + 16 * g;
+    int s0, s1;
+    skv_rows_k_slice<NWV>(K / 64, wave, s0, s1);
     f32x4 acc[RT][MT];
 #pragma unroll
     for (int r = 0; r < RT; ++r)
@@ -241,80 +192,31 @@ __global__ __launch_bounds__(NWV * 64) void skv_rows_gemm2_fp8_kernel(const uint
             }
         }
     }
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s_red[wave][t][r][4 * g + i][a] = acc[r][t][i];
-    __syncthreads();
-    if (SILU_PAIR) {
-        for (int o = tid; o < RT * 8 * M; o += NWV * 64) {
-            const int tok = o / (RT * 8), j = o % (RT * 8), r = j >> 3, i = j & 7, idx = (blockIdx.x * RT + r) * 8 + i;
-            if (idx < I) {
-                float gs = 0.f, us = 0.f;
-#pragma unroll
-                for (int w = 0; w < NWV; ++w) {
-                    gs += s_red[w][tok >> 4][r][i][tok & 15];
-                    us += s_red[w][tok >> 4][r][i + 8][tok & 15];
-                }
-                const float gg = bfr(scale[idx] * gs), uu = bfr(scale[I + idx] * us);  // the projection outputs are bf16 tensors
-                Y[(size_t)tok * I + idx] = f2bf(bfr(gg / (1.0f + __expf(-gg))) * uu);
-            }
-        }
-    } else {
-        for (int o = tid; o < RT * 16 * M; o += NWV * 64) {
-            const int tok = o / (RT * 16), j = o % (RT * 16), r = j >> 4, rr = j & 15, n = (blockIdx.x * RT + r) * 16 + rr;
-            if (n < N) {
-                float t = 0.f;
-#pragma unroll
-                for (int w = 0; w < NWV; ++w) t += s_red[w][tok >> 4][r][rr][tok & 15];
-                t *= scale[n];                   // the row's scale: one f32 multiply after the reduction
-                Y[(size_t)tok * N + n] = f2bf(bias ? bfr(t) + bf2f(bias[n]) : t);
-            }
-        }
-    }
+    skv_rows_epilogue<SILU_PAIR, true, false, NWV>(acc, tid, a, g, scale, bias, Y, N, M, I);
 }
 
-template <bool SILU_PAIR, int MT, int RT, int NWV, int U = 4>
-static void launch_rows2_fp8(const void* W, const void* scale, const void* X, const void* bias, void* Y, int M, int N, int K, int I,
-                             hipStream_t st) {
-    const int tiles = SILU_PAIR ? (I + 7) / 8 : (N + 15) / 16;
-    hipLaunchKernelGGL((skv_rows_gemm2_fp8_kernel<SILU_PAIR, MT, RT, NWV, U>), dim3((tiles + RT - 1) / RT), dim3(NWV * 64), 0, st,
-                       (const uint8_t*)W, (const float*)scale, (const bf16_t*)X, (const bf16_t*)bias, (bf16_t*)Y, N, K, M, I);
-}
-
-template <bool SILU_PAIR, bool PAIRX, int MT, int U = RG8_U>
-static void launch_rows1_fp8(const void* W, const void* scale, const void* X, const void* bias, void* Y, int M, int N, int K, int I,
-                             hipStream_t st) {
-    hipLaunchKernelGGL((skv_rows_gemm_fp8_kernel<SILU_PAIR, PAIRX, MT, U>), dim3(SILU_PAIR ? (I + 7) / 8 : (N + 15) / 16),
-                       dim3(RG8_WAVES * 64), 0, st, (const uint8_t*)W, (const float*)scale, (const bf16_t*)X, (const bf16_t*)bias,
-                       (bf16_t*)Y, N, K, M, I);
-}
-
-// Kernel and shape per (token rows, projection).  The thresholds are those of launch_rows (skv_rows_gemm.hip), which were
-// measured for bf16 WEIGHTS: for this kernel they are a STARTING POINT, NOT A RESULT - nothing here has been timed with FP8
-// weights yet.  An entry changes only with numbers from tools/time_rows_gemm.py --fp8 (profiles/fp8_rows_timing.txt).
-//     rows <= 8            -> first generation, paired token operand
-//     rows <= 16           -> first generation; 6144 <= N < 16384: 2x8
-//     rows <= 32           -> N >= 16384: 4x4; 6144 <= N < 16384: 2x8; K >= 8192: 1x8; else first generation, two token tiles
 // k-steps in flight per wave (weight loads of 16 B per lane; every k-step adds 2 * MT token loads): 8 with the paired token
 // operand, 4 in the other first-generation shapes (two workgroups fit a CU's registers; 8 steps leave room for one), 4 in the
-// second generation, 2 in its 4x4 shape (16 loads per step pair).  Like the thresholds: chosen from the register counts, not timed.
-template <bool SILU_PAIR>
-static void launch_rows_fp8(const void* W, const void* scale, const void* X, const void* bias, void* Y, int M, int N, int K, int I,
-                            hipStream_t st) {
-    const bool mid = N >= 6144 && N < 16384;
-    if (M <= 8) return launch_rows1_fp8<SILU_PAIR, true, 1>(W, scale, X, bias, Y, M, N, K, I, st);
-    if (M <= 16) {
-        if (mid) return launch_rows2_fp8<SILU_PAIR, 1, 2, 8>(W, scale, X, bias, Y, M, N, K, I, st);
-        return launch_rows1_fp8<SILU_PAIR, false, 1, 4>(W, scale, X, bias, Y, M, N, K, I, st);
+// second generation, 2 in its 4x4 shape (16 loads per step pair).  Like the thresholds of skv_rows_pick for this format:
+// chosen from the register counts, not timed.
+struct RowsFp8 {
+    const uint8_t* W;
+    const float* scale;
+    const bf16_t *X, *bias;
+    bf16_t* Y;
+    int M, N, K;
+    hipStream_t st;
+    template <bool SILU_PAIR, bool PAIRX, int MT>
+    void gen1(int grid, int I) const {
+        hipLaunchKernelGGL((skv_rows_gemm_fp8_kernel<SILU_PAIR, PAIRX, MT, PAIRX ? RG8_U : 4>), dim3(grid), dim3(RG8_WAVES * 64), 0, st,
+                           W, scale, X, bias, Y, N, K, M, I);
     }
-    if (N >= 16384) return launch_rows2_fp8<SILU_PAIR, 2, 4, 4, 2>(W, scale, X, bias, Y, M, N, K, I, st);
-    if (mid) return launch_rows2_fp8<SILU_PAIR, 2, 2, 8>(W, scale, X, bias, Y, M, N, K, I, st);
-    if (K >= 8192) return launch_rows2_fp8<SILU_PAIR, 2, 1, 8>(W, scale, X, bias, Y, M, N, K, I, st);
-    return launch_rows1_fp8<SILU_PAIR, false, 2, 4>(W, scale, X, bias, Y, M, N, K, I, st);
-}
+    template <bool SILU_PAIR, int MT, int RT, int NWV>
+    void gen2(int grid, int I) const {
+        hipLaunchKernelGGL((skv_rows_gemm2_fp8_kernel<SILU_PAIR, MT, RT, NWV, RT == 4 ? 2 : 4>), dim3(grid), dim3(NWV * 64), 0, st,
+                           W, scale, X, bias, Y, N, K, M, I);
+    }
+};
 
 extern "C" int skv_linear_rows_fp8(const void* W8, const void* scale, const void* X, const void* bias, void* Y, int M, int N, int K,
                                    int fuse_silu_mul, skv_stream_t stream) {
@@ -322,7 +224,6 @@ extern "C" int skv_linear_rows_fp8(const void* W8, const void* scale, const void
     if (!W8 || !scale || !X || !Y || M < 1 || N < 1) return SKV_ERR_ARG;
     if (fuse_silu_mul && (N % 2 || bias)) return SKV_ERR_ARG;
     if (M > 32 || K % 64 || K < 64) return SKV_ERR_UNSUPPORTED;
-    if (fuse_silu_mul) launch_rows_fp8<true>(W8, scale, X, nullptr, Y, M, N, K, N / 2, (hipStream_t)stream);
-    else launch_rows_fp8<false>(W8, scale, X, bias, Y, M, N, K, 0, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
+    const RowsFp8 l{(const uint8_t*)W8, (const float*)scale, (const bf16_t*)X, (const bf16_t*)bias, (bf16_t*)Y, M, N, K, (hipStream_t)stream};
+    return skv_rows_dispatch(l, M, N, K, fuse_silu_mul != 0);
 }

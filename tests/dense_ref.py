@@ -233,6 +233,24 @@ def range_max_ref(y):
     return order_keys(y.reshape(-1)).view(-1, 16).max(-1).values
 
 
+# ------------------------------------------------------------------------------------------------------------ rows GEMM
+def expected_branch(M, N, K):
+    """The kernel skv_rows_pick (skv_rows_frame.h) launches for bf16 and for FP8 weights alike, from the thresholds its table
+    documents: up to 8 token rows the first generation with the paired token operand; up to 16 the first generation, 2x8
+    where 6144 <= N < 16384; from 17 on two token tiles: 4x4 for N >= 16384, 2x8 in the middle range, 1x8 for K >= 8192, else
+    the first generation."""
+    mid = 6144 <= N < 16384
+    if M <= 8:
+        return "g1 paired"
+    if M <= 16:
+        return "g2 1/2x8" if mid else "g1"
+    if N >= 16384:
+        return "g2 2/4x4"
+    if mid:
+        return "g2 2/2x8"
+    return "g2 2/1x8" if K >= 8192 else "g1 two tiles"
+
+
 # ------------------------------------------------------------------------------------ random-data companion (flip shares)
 RANDOM_GEMV = dict(N=4101, K=13696, M=1, seed=4101 + 13696)
 RANDOM_ROWS = dict(N=6160, K=1056, M=17, seed=17 + 6160 + 1056)

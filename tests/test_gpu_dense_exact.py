@@ -1,5 +1,5 @@
 """GPU: the dense kernels of a decode layer - skv_gemv.hip (every template path of launch_gemv), skv_rows_gemm.hip (every
-branch of launch_rows), skv_dense.hip, the QKV epilogue and the k/v role of skv_kvproj.h, the sampler's range keys - against
+branch of skv_rows_pick), skv_dense.hip, the QKV epilogue and the k/v role of skv_kvproj.h, the sampler's range keys - against
 tests/dense_ref.py.  The inputs are built so that the exact result is a small integer: every order of
 f32 accumulation gives it and bf16 holds it, so the comparison is on raw bits and one dropped, doubled or misplaced k element
 fails it.  SiLU (fast exp) and RMSNorm on random data (f32 rsqrt) carry bounds from the number formats alone.  No expected
@@ -9,6 +9,7 @@ import torch
 
 import dense_ref as dr
 import util
+from dense_ref import expected_branch
 from test_gpu_kv_proj_split import PLACEMENTS, run_selection, select_inputs
 
 pytestmark = pytest.mark.gpu
@@ -484,26 +485,10 @@ ROWS_K = (32, 96, 288, 1056, 8224)
 ROWS_N = (48, 2 * 1003, 6160, 16400)          # 2 * 1003: the SiLU pair form
 
 
-def expected_branch(M, N, K):
-    """The kernel launch_rows picks, from the thresholds its table documents (skv_rows_gemm.hip): up to 8 token rows the first
-    generation with the paired token operand; up to 16 the first generation, 2x8 where 6144 <= N < 16384; from 17 on two token
-    tiles: 4x4 for N >= 16384, 2x8 in the middle range, 1x8 for K >= 8192, else the first generation."""
-    mid = 6144 <= N < 16384
-    if M <= 8:
-        return "g1 paired"
-    if M <= 16:
-        return "g2 1/2x8" if mid else "g1"
-    if N >= 16384:
-        return "g2 2/4x4"
-    if mid:
-        return "g2 2/2x8"
-    return "g2 2/1x8" if K >= 8192 else "g1 two tiles"
-
-
 def test_rows_gemm_shapes_reach_every_branch():
     reached = {expected_branch(M, N, K) for M in ROWS_M for N in ROWS_N for K in ROWS_K}
     assert reached == {"g1 paired", "g2 1/2x8", "g1", "g2 2/4x4", "g2 2/2x8", "g2 2/1x8", "g1 two tiles"}
-    assert len(reached) == 7                                               # the seven return statements of launch_rows
+    assert len(reached) == 7                                               # the seven return statements of skv_rows_pick
     assert expected_branch(17, 48, 8224) == "g2 2/1x8" and expected_branch(17, 48, 1056) == "g1 two tiles"
     assert expected_branch(16, 6160, 32) == "g2 1/2x8" and expected_branch(32, 16400, 32) == "g2 2/4x4"
 

@@ -10,6 +10,7 @@ import torch
 import dense_ref as dr
 import fp8_rows_ref as rr
 import util
+from dense_ref import expected_branch
 from test_gpu_gemv_fp8_exact import (DEV, PAD, SENT, _L, assert_bits, assert_silu, dev16, fp8_weights, pair_scales, pow2_scales,
                                      scaled, sentinel_buf)
 
@@ -20,26 +21,10 @@ ROWS_K = (64, 192, 576, 2112, 8256)           # K / 64 = 1, 3, 9, 33, 129
 ROWS_N = (48, 2 * 1003, 6160, 16400)          # 2 * 1003: the SiLU pair form
 
 
-def expected_branch(M, N, K):
-    """The kernel launch_rows_fp8 picks (skv_rows_gemm_fp8.hip; the thresholds of launch_rows): up to 8 token rows the first
-    generation with the paired token operand; up to 16 the first generation, 2x8 where 6144 <= N < 16384; from 17 on two token
-    tiles: 4x4 for N >= 16384, 2x8 in the middle range, 1x8 for K >= 8192, else the first generation."""
-    mid = 6144 <= N < 16384
-    if M <= 8:
-        return "g1 paired"
-    if M <= 16:
-        return "g2 1/2x8" if mid else "g1"
-    if N >= 16384:
-        return "g2 2/4x4"
-    if mid:
-        return "g2 2/2x8"
-    return "g2 2/1x8" if K >= 8192 else "g1 two tiles"
-
-
 def test_rows_fp8_shapes_reach_every_branch():
     reached = {expected_branch(M, N, K) for M in ROWS_M for N in ROWS_N for K in ROWS_K}
     assert reached == {"g1 paired", "g2 1/2x8", "g1", "g2 2/4x4", "g2 2/2x8", "g2 2/1x8", "g1 two tiles"}
-    assert len(reached) == 7                                               # the seven return statements of launch_rows_fp8
+    assert len(reached) == 7                                               # the seven return statements of skv_rows_pick
     assert expected_branch(17, 48, 8256) == "g2 2/1x8" and expected_branch(17, 48, 2112) == "g1 two tiles"
     assert expected_branch(16, 6160, 64) == "g2 1/2x8" and expected_branch(32, 16400, 64) == "g2 2/4x4"
     # the SiLU pair form (N = 2006) and the plain form both reach the two first-generation tile counts and the 1x8 shape

@@ -1,18 +1,48 @@
 #!/usr/bin/env python3
-"""Bit identity of the decode GEMV entries between two builds of the library.
+"""Bit identity of the decode GEMV entries and the small-M rows entries between two builds of the library.
 
     SKV_LIB_PATH=<library A> python tools/gemv_ab_bits.py --dump a.pt      (one fresh process per library)
     python tools/gemv_ab_bits.py --dump b.pt
     python tools/gemv_ab_bits.py --compare a.pt b.pt
 
 --dump runs every public GEMV entry of both formats (skv_gemv.hip, skv_gemv_fp8.hip) on seeded inputs - the shapes of the
-exact tests and the Llama-3.1-8B shapes - and stores every output tensor as raw 16-bit words; --compare is torch.equal."""
+exact tests and the Llama-3.1-8B shapes - and the two rows entries (skv_rows_gemm.hip, skv_rows_gemm_fp8.hip) on Gaussian data, and
+stores every output tensor as raw 16-bit words; --compare is torch.equal."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")]
 import torch
 
 DEV = "cuda:0"
+# the rows entries: token rows, plain N (with and without bias), the SiLU pair N, K per format, the Llama-3.1-8B projections
+ROWS_M, ROWS_N, ROWS_SILU_N = (2, 8, 9, 16, 17, 32), (48, 6160, 16400), 2 * 1003
+ROWS_K = {"bf16": (96, 288, 1056, 8224), "fp8": (192, 576, 2112, 8256)}
+ROWS_LLAMA = ((6144, 4096, 0), (4096, 4096, 0), (28672, 4096, 1), (4096, 14336, 0))       # (N, K, silu) at M = 8 and 24
+# per format: elements of a k-step, then (waves per workgroup, k-steps in flight) of every branch of skv_rows_pick
+ROWS_SHAPES = {"bf16": (32, {"g1 paired": (8, 8), "g1": (8, 8), "g1 two tiles": (8, 8), "g2 1/2x8": (8, 4), "g2 2/2x8": (8, 4),
+                             "g2 2/1x8": (8, 4), "g2 2/4x4": (4, 4)}),
+               "fp8": (64, {"g1 paired": (8, 8), "g1": (8, 4), "g1 two tiles": (8, 4), "g2 1/2x8": (8, 4), "g2 2/2x8": (8, 4),
+                            "g2 2/1x8": (8, 4), "g2 2/4x4": (4, 2)})}
+
+
+def rows_coverage(fmt):
+    """The small rows shapes reach all seven branches, and in either generation a wave that runs unrolled batches, one that runs
+    single-step tails and a K with fewer k-steps than waves (the order of the f32 sums differs between those paths)."""
+    from dense_ref import expected_branch
+    step, shapes = ROWS_SHAPES[fmt]
+    reached = set()
+    for M in ROWS_M:
+        for N in ROWS_N + (ROWS_SILU_N,):
+            for K in ROWS_K[fmt]:
+                b = expected_branch(M, N, K)
+                nwv, u = shapes[b]
+                S = K // step
+                per = -(-S // nwv)
+                last = S - per * ((S - 1) // per)                       # steps of the last wave that has any
+                reached |= {b, (b[:2], "batch") if per >= u else None, (b[:2], "tail") if per % u or last % u else None,
+                            (b[:2], "fewer steps than waves") if S < nwv else None}
+    want = set(shapes) | {(g, c) for g in ("g1", "g2") for c in ("batch", "tail", "fewer steps than waves")}
+    assert reached - {None} == want, (fmt, want - reached)
 
 
 def dump(path):
@@ -137,6 +167,23 @@ def dump(path):
                 L.skv_gemv_near_pull_fp8(p(w8), p(sc), p(xd), p(b), p(y), N, Kd, *a, st)
             keep(f"near down {fmt} {N}", rc, y, c.near_published_ids(0).to(torch.int32).view(torch.int16))
         del c
+    # the rows entries: Gaussian weights and activations (the integer banks of the exact tests are blind to the summation order)
+    for fmt in ("bf16", "fp8"):
+        rows_coverage(fmt)
+        cases = [(M, N, K, N == ROWS_SILU_N) for N in ROWS_N + (ROWS_SILU_N,) for K in ROWS_K[fmt] for M in ROWS_M]
+        cases += [(M, N, K, bool(silu)) for N, K, silu in ROWS_LLAMA for M in (8, 24)]
+        w = None
+        for M, N, K, silu in cases:
+            if w is None or w.shape != (N, K):
+                w, w8, sc = both(N, K)
+                xr, b = rnd(max(ROWS_M), K), rnd(N)
+            xm = xr[:M].contiguous()
+            for bias in ((None,) if silu else (None, b)):
+                No = N // 2 if silu else N
+                y = buf(M * No)
+                rc = L.skv_linear_rows_bf16(p(w), p(xm), p(bias), p(y), M, N, K, int(silu), st) if fmt == "bf16" else \
+                    L.skv_linear_rows_fp8(p(w8), p(sc), p(xm), p(bias), p(y), M, N, K, int(silu), st)
+                keep(f"rows_{fmt} M {M} {N}x{K} silu {int(silu)} bias {bias is not None}", rc, y)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(out, path)
     print(f"{len(out)} tensors from {_lib.LIB_PATH} -> {path}")
