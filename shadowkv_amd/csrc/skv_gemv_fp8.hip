@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void skv_gemv_fp8_kernel(const uint8_t* __rest
     float tot[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) tot[r] = sc[r] * skv_gemv_row_total(acc[r]);   // the row's scale: one f32 multiply after the reduction
-    skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias, y, qe, range_max);
+    skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias, y, qe, range_max, x);
 }
 
 // every check of the GEMV's own arguments; host only, before any HIP call

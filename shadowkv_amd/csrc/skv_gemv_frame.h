@@ -62,14 +62,35 @@ __device__ __forceinline__ float skv_gemv_row_total(const f32x2 (&acc)[4]) {
     return wave_tree_sum(s);
 }
 
+// The operands of the epilogue: skv_gemv_epilogue_fetch requests them - the bias values of the wave's rows (the down
+// projection of the call-order path carries the residual there), or what skv_qkv_epilogue_fetch names - and belongs IN FRONT
+// of the weight stream (QKV: skv_gemv_epilogue_fetch_cs behind the first weight request); skv_gemv_epilogue then holds
+// arithmetic and stores only.  The addresses are the wave's and the loads unconditional (skv_kvproj.h says why); `spare` is a
+// readable bf16 for the values a launch does not have.  (A launch without the QKV epilogue uses the bias field alone.)
+template <int R, bool SILU_PAIR, bool QKV>
+__device__ __forceinline__ QkvOperands<R> skv_gemv_epilogue_fetch(const int (&rows)[R], int unit0, int N, const bf16_t* __restrict__ bias,
+                                                                  const QkvEpilogue& qe, const bf16_t* spare) {
+    if constexpr (QKV) return skv_qkv_epilogue_fetch<R>(qe, bias, rows, unit0, spare);
+    QkvOperands<R> op{};
+    if constexpr (!SILU_PAIR) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) op.bias[r] = *(bias ? bias + (unit0 + r < N ? unit0 + r : 0) : spare);
+    }
+    return op;
+}
+template <int R, bool QKV>
+__device__ __forceinline__ void skv_gemv_epilogue_fetch_cs(QkvOperands<R>& op, const QkvEpilogue& qe, const int (&rows)[R], int unit0) {
+    if constexpr (QKV) skv_qkv_epilogue_fetch_cs<R>(op, qe, rows, unit0);
+}
+
 // tot[R] -> the launch's outputs (lane 0 of every wave writes)
 template <int R, bool SILU_PAIR, bool QKV, bool RMAX>
 __device__ __forceinline__ void skv_gemv_epilogue(const int (&rows)[R], const float (&tot)[R], int unit0, int bx, int tid, int N,
-                                                  int I, const bf16_t* __restrict__ bias, bf16_t* __restrict__ y,
+                                                  int I, bool has_bias, const QkvOperands<R>& op, bf16_t* __restrict__ y,
                                                   const QkvEpilogue& qe, uint16_t* __restrict__ range_max) {
     const int lane = tid & 63, wave = tid >> 6;
-    if (QKV) {
-        if (lane == 0 && unit0 < N) skv_qkv_epilogue<R>(qe, bias, rows, tot, unit0);
+    if constexpr (QKV) {
+        if (lane == 0 && unit0 < N) skv_qkv_epilogue_apply<R>(qe, has_bias, op, rows, tot, unit0);
         return;
     }
     __shared__ uint32_t s_kmax[RMAX ? 4 : 1];
@@ -88,7 +109,7 @@ __device__ __forceinline__ void skv_gemv_epilogue(const int (&rows)[R], const fl
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int n = unit0 + r;
-                const bf16_t o = f2bf(bias ? bfr(tot[r]) + bf2f(bias[n < N ? n : 0]) : tot[r]);
+                const bf16_t o = f2bf(has_bias ? bfr(tot[r]) + bf2f(op.bias[r]) : tot[r]);
                 if (n < N) y[n] = o;
                 if (RMAX) kmax = max(kmax, skv_bf16_order_key(o));
             }
@@ -99,6 +120,19 @@ __device__ __forceinline__ void skv_gemv_epilogue(const int (&rows)[R], const fl
         __syncthreads();
         if (tid == 0) range_max[bx] = (uint16_t)max(max(s_kmax[0], s_kmax[1]), max(s_kmax[2], s_kmax[3]));
     }
+}
+// fetch and apply back to back, for a kernel that leaves the epilogue's loads behind its reduction (a wave past the end of a
+// QKV launch neither loads nor stores)
+template <int R, bool SILU_PAIR, bool QKV, bool RMAX>
+__device__ __forceinline__ void skv_gemv_epilogue(const int (&rows)[R], const float (&tot)[R], int unit0, int bx, int tid, int N,
+                                                  int I, const bf16_t* __restrict__ bias, bf16_t* __restrict__ y,
+                                                  const QkvEpilogue& qe, uint16_t* __restrict__ range_max, const bf16_t* spare) {
+    QkvOperands<R> op{};
+    if (!QKV || unit0 < N) {
+        op = skv_gemv_epilogue_fetch<R, SILU_PAIR, QKV>(rows, unit0, N, bias, qe, spare);
+        skv_gemv_epilogue_fetch_cs<R, QKV>(op, qe, rows, unit0);
+    }
+    skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias != nullptr, op, y, qe, range_max);
 }
 
 // Host: the kernel instance and the grid of a launch, for both formats.  L is the format's launcher: it holds the launch's

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void skv_gemv_mxfp4_kernel(const uint8_t* __re
     float tot[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) tot[r] = skv_gemv_row_total(acc[r]);   // (no multiply after the reduction: the scales are in the weights)
-    skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias, y, qe, range_max);
+    skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias, y, qe, range_max, x);
 }
 
 // every check of the GEMV's own arguments; host only, before any HIP call
