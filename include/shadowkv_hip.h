@@ -738,6 +738,20 @@ SKV_EXPORT int skv_gemv_near_pull_mxfp4(const void* W4, const void* scale_e8m0, 
                            void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
                            const void* v_host, long long host_block_stride, int pull_parts, int list, skv_stream_t stream);
 
+/* ---- part 9: weight-only MXFP4 for 2..32 token rows -------------------------------------------------- */
+
+/* The MXFP4 sibling of skv_linear_rows_bf16 / skv_linear_rows_fp8: 2..32 token rows (1 works too) against the W4 / scale_e8m0 pair
+ * of part 8 (same nibble order, one e8m0 byte per 32 consecutive elements of a row), the nibbles streamed once.  X [M][K] bf16,
+ * Y [M][N] bf16 ([M][N/2] with fuse_silu_mul, W4 = [gate; up]), bias bf16 [N] or null.  Per output
+ * t = sum_k f32(2^s(n, k / 32) * e2m1(n, k)) * f32(X[m][k]): the block scale is applied to the weight (exact in bf16 for scale
+ * bytes 27..227, for which the contract is stated), f32 accumulation (v_mfma_f32_16x16x32_bf16 on the exactly converted weights;
+ * no FP4 / FP8 activation, no scaled MFMA), the split-K partials summed in wave order, no multiply after the reduction; then the
+ * epilogue of skv_linear_rows_bf16: bf16(t), bf16(bf16r(t) + bias[n]), or bf16(bf16r(silu(bf16r(t_g))) * bf16r(t_u)).
+ * Checked on the host before any HIP call: a null W4 / scale_e8m0 / X / Y, M < 1, N < 1, fuse_silu_mul with an odd N or a bias:
+ * SKV_ERR_ARG; M > 32, K % 128 != 0 or K < 128: SKV_ERR_UNSUPPORTED.  W4 and X 16-byte aligned. */
+SKV_EXPORT int skv_linear_rows_mxfp4(const void* W4, const void* scale_e8m0, const void* X, const void* bias, void* Y, int M, int N,
+                          int K, int fuse_silu_mul, skv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,7 @@ _SIGS = {
     "skv_host_free": (c_int, [c_p]),
     "skv_linear_rows_bf16": (c_int, [c_p] * 4 + [c_int] * 4 + [c_p]),
     "skv_linear_rows_fp8": (c_int, [c_p] * 5 + [c_int] * 4 + [c_p]),
+    "skv_linear_rows_mxfp4": (c_int, [c_p] * 5 + [c_int] * 4 + [c_p]),
     "skv_sparse_attention": (c_int, [c_p] * 6 + [c_int, c_int, c_ll] + [c_int] * 5 + [c_f, c_p]),
     "skv_sparse_attention_slots": (c_int, [c_p] * 6 + [c_int, c_int, c_ll] + [c_int] * 5 + [c_f, c_p] + [c_int] * 3 + [c_p]),
     "skv_prefill_attention": (c_int, [c_p] * 4 + [c_int] * 6 + [c_ll] * 9 + [c_f, c_p]),

@@ -135,7 +135,7 @@ class DecoderLM:
                  attn_mode="shadowkv_cpu", sparse_budget=2048, rank=160, chunk_size=8, random_init=True, seed=1234,
                  num_layers=None, chunk_layout="reference", v_offload=True, overlap_attention=False, max_new_tokens=1024,
                  resident_sets=None, minference=False, minference_pattern=None, weight_dtype="bf16", fp8_rows="fallback",
-                 v_dtype="bf16"):
+                 v_dtype="bf16", mxfp4_rows="fallback"):
         if weight_dtype not in WEIGHT_DTYPES:       # (before anything is allocated)
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
         if v_dtype not in tensor_op.V_DTYPES:
@@ -147,6 +147,11 @@ class DecoderLM:
         # FP8 weights with 2..32 sequences: "native" = skv_linear_rows_fp8, "fallback" = dequantise + F.linear (DESIGN.md section
         # 10.1); read only where a w_scale is passed, so it is inert on a bf16 model until quantize_weights()
         self.fp8_rows = fp8_rows
+        if mxfp4_rows not in tensor_op.MXFP4_ROWS_MODES:
+            raise ValueError(f"mxfp4_rows must be one of {tensor_op.MXFP4_ROWS_MODES}, got {mxfp4_rows!r}")
+        # MXFP4 weights with 2..32 sequences: "native" = skv_linear_rows_mxfp4, "fallback" = dequantise + F.linear (DESIGN.md
+        # section 12.1); read only with an MXFP4 pair, so it is inert on a bf16 or FP8 model
+        self.mxfp4_rows = mxfp4_rows
         if chunk_layout not in ("reference", "inplace"):
             raise ValueError("chunk_layout must be 'reference' (hits compacted to the front, the reference's slot order) "
                              "or 'inplace' (hits keep their slots, misses take the freed slots)")
@@ -297,7 +302,8 @@ class DecoderLM:
             sc["i"] ^= 1                                        # (a new layer: the other buffer set)
             _, qkv = tensor_op.norm_linear_decode(hidden_states, None, layer.input_layernorm_weight,
                                                   layer.input_layernorm_variance_epsilon, layer.wqkv, layer.bqkv,
-                                                  out=sc["sets"][sc["i"]]["qkv"], w_scale=layer.wqkv_scale, fp8_rows=self.fp8_rows)
+                                                  out=sc["sets"][sc["i"]]["qkv"], w_scale=layer.wqkv_scale, fp8_rows=self.fp8_rows,
+                                                  mxfp4_rows=self.mxfp4_rows)
         else:
             hs = tensor_op.layer_norm(hidden_states, layer.input_layernorm_variance_epsilon, layer.input_layernorm_weight)
             qkv = F.linear(hs, layer.prefill_weight("wqkv"), layer.bqkv)
@@ -363,7 +369,8 @@ class DecoderLM:
         if attn_output.shape[1] == 1 and attn_output.is_cuda:       # one decode token per sequence: native kernels
             sc = self._decode_scratch(attn_output.shape[0])
             cur = sc["sets"][sc["i"]]
-            o = tensor_op.linear_decode(attn_output, layer.wo, out=cur["o"], w_scale=layer.wo_scale, fp8_rows=self.fp8_rows)
+            o = tensor_op.linear_decode(attn_output, layer.wo, out=cur["o"], w_scale=layer.wo_scale, fp8_rows=self.fp8_rows,
+                                        mxfp4_rows=self.mxfp4_rows)
             # (one sequence on the ShadowKV cache with near_fetch: the launch's first workgroups stage this step's near misses)
             near = None
             if attn_output.shape[0] == 1 and self.attn_mode != "full" and getattr(layer, "layer_idx", None) is not None:
@@ -371,13 +378,15 @@ class DecoderLM:
             residual, act = tensor_op.norm_linear_decode(o, residual, layer.post_attention_layernorm_weight,
                                                          layer.post_attention_layernorm_variance_epsilon,
                                                          layer.gate_up_proj, fuse_silu_mul=True, out=cur["act"], h_out=cur["h"],
-                                                         near_pull=near, w_scale=layer.gate_up_proj_scale, fp8_rows=self.fp8_rows)
+                                                         near_pull=near, w_scale=layer.gate_up_proj_scale, fp8_rows=self.fp8_rows,
+                                                         mxfp4_rows=self.mxfp4_rows)
             if residual.shape[0] == 1:      # one sequence: the residual rides in the GEMV's bias slot (bf16(W.act) + residual,
                 #                             rounded like the separate add: same bits, one launch less)
                 near1 = None if near is None else self.kv_cache.near_pull_args(layer.layer_idx, 1)
                 return tensor_op.linear_decode(act, layer.down_proj, bias=residual, out=cur["out"], near_pull=near1,
-                                               w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows)
-            down = tensor_op.linear_decode(act, layer.down_proj, out=cur["down"], w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows)
+                                               w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows, mxfp4_rows=self.mxfp4_rows)
+            down = tensor_op.linear_decode(act, layer.down_proj, out=cur["down"], w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows,
+                                           mxfp4_rows=self.mxfp4_rows)
             return torch.add(residual, down, out=cur["out"])
         # (prefill: an FP8 layer's matrices are dequantised to bf16 temporaries as they are reached, each freed after its GEMM)
         hs = residual + F.linear(attn_output, layer.prefill_weight("wo"))
@@ -596,7 +605,7 @@ class DecoderLM:
                     x, residual, layer.input_layernorm_weight, layer.input_layernorm_variance_epsilon, layer.wqkv,
                     layer.bqkv, self.cos_sin_cache, pos, row_idx, kbuf, vbuf, self.num_heads,
                     self.num_key_value_heads, q_override=None if q_table is None else q_table[l], w_scale=layer.wqkv_scale,
-                    fp8_rows=self.fp8_rows)
+                    fp8_rows=self.fp8_rows, mxfp4_rows=self.mxfp4_rows)
                 self.kv_proj_fused_launches += 1
             if overlap:
                 attn = c.select_fetch_attend_inplace(l, q, self.cos_sin_cache, kv_len=kv_len, kv_len_dev=kv_len_dev,
@@ -614,16 +623,18 @@ class DecoderLM:
                         c.fetch_kv_follows = False
                     c.fetch_kv(l, ids, self.cos_sin_cache)
                 attn = tensor_op.sparse_attention_decode(q, kbuf, vbuf, kv_len=kv_len, kv_len_dev=kv_len_dev, **slot_args)
-            o = tensor_op.linear_decode(attn.reshape(bs, 1, self.hidden_size), layer.wo, w_scale=layer.wo_scale, fp8_rows=self.fp8_rows)
+            o = tensor_op.linear_decode(attn.reshape(bs, 1, self.hidden_size), layer.wo, w_scale=layer.wo_scale, fp8_rows=self.fp8_rows,
+                                        mxfp4_rows=self.mxfp4_rows)
             # residual add + RMSNorm ride in the gate/up GEMV's block-cooperative prologue (one launch when bs == 1
             # and hidden == 4096, bit-identical to add_rmsnorm + GEMV; otherwise norm_linear_decode splits it)
             residual, act = tensor_op.norm_linear_decode(o, residual, layer.post_attention_layernorm_weight,
                                                          layer.post_attention_layernorm_variance_epsilon,
                                                          layer.gate_up_proj, fuse_silu_mul=True,
                                                          near_pull=None if full or bs != 1 else c.near_pull_args(l),
-                                                         w_scale=layer.gate_up_proj_scale, fp8_rows=self.fp8_rows)
+                                                         w_scale=layer.gate_up_proj_scale, fp8_rows=self.fp8_rows,
+                                                         mxfp4_rows=self.mxfp4_rows)
             x = tensor_op.linear_decode(act, layer.down_proj, near_pull=None if full or bs != 1 else c.near_pull_args(l, 1),
-                                        w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows)
+                                        w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows, mxfp4_rows=self.mxfp4_rows)
         V = self.lm_head.shape[0]
         rm = None
         if self.sampler_ranges and not as_float and x.is_cuda and tensor_op.range_max_supported(x.numel(), x.shape[-1], V):
@@ -632,7 +643,8 @@ class DecoderLM:
             rm = self._range_max
         self._last_range_max = rm
         _, logits = tensor_op.norm_linear_decode(x, residual, self.norm_weight, self.norm_variance_epsilon, self.lm_head,
-                                                 range_max=rm, w_scale=self.lm_head_scale, fp8_rows=self.fp8_rows)
+                                                 range_max=rm, w_scale=self.lm_head_scale, fp8_rows=self.fp8_rows,
+                                                 mxfp4_rows=self.mxfp4_rows)
         return logits.float() if as_float else logits        # (the native sampler reads the bf16 row as it is)
 
     def get_ctx(self, input_ids):
@@ -647,7 +659,7 @@ class DecoderLM:
             hs = self.layer_compute(self.layers[idx], idx, hs, position_ids)
         if hs.shape[1] == 1 and hs.is_cuda:
             _, logits = tensor_op.norm_linear_decode(hs, None, self.norm_weight, self.norm_variance_epsilon, self.lm_head,
-                                                     w_scale=self.lm_head_scale, fp8_rows=self.fp8_rows)
+                                                     w_scale=self.lm_head_scale, fp8_rows=self.fp8_rows, mxfp4_rows=self.mxfp4_rows)
             return logits.float() if as_float else logits    # (bf16: tensor_op.sample_token then samples in one launch)
         hs = tensor_op.layer_norm(hs, self.norm_variance_epsilon, self.norm_weight)
         return F.linear(hs, self._lm_head_prefill()).float()

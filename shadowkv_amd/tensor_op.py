@@ -174,20 +174,34 @@ def _mxfp4_native(x, w, w_scale, rows):
     return rows == 1 and K % MXFP4_BLOCK == 0 and K >= MXFP4_MIN_K and x.is_contiguous() and w.is_contiguous() and w_scale.is_contiguous()
 
 
+def _mxfp4_native_rows(x, w, w_scale, rows):
+    """Shapes skv_linear_rows_mxfp4 takes: 2..MAX_GEMV_ROWS token rows on the GPU, K % 128 == 0, contiguous operands."""
+    return 2 <= rows <= MAX_GEMV_ROWS and x.shape[-1] % 128 == 0 and x.is_cuda and x.is_contiguous() and w.is_contiguous() \
+        and w_scale.is_contiguous()
+
+
+MXFP4_ROWS_MODES = ("fallback", "native")    # what 2..MAX_GEMV_ROWS token rows against an MXFP4 pair take (linear_decode)
+
+
+def _mxfp4_rows_check(mxfp4_rows):
+    if mxfp4_rows not in MXFP4_ROWS_MODES:
+        raise ValueError(f"mxfp4_rows must be one of {MXFP4_ROWS_MODES}, got {mxfp4_rows!r}")
+
+
 mxfp4_native_calls = 0    # native MXFP4 launches / dequantising fallbacks taken so far (diagnostics; the tests read them)
 mxfp4_fallback_calls = 0
 
 
 def _mxfp4_linear_fallback(x, w, w_scale, bias, fuse_silu_mul):
-    """CORRECT AND SLOW: the weights are dequantised to a bf16 temporary on every call, then F.linear (more than one token row,
-    K < 1024, non-contiguous operands)."""
+    """CORRECT AND SLOW: the weights are dequantised to a bf16 temporary on every call, then F.linear (more than one token row
+    unless mxfp4_rows="native" serves them, K < 1024 at one row, non-contiguous operands)."""
     global mxfp4_fallback_calls
     mxfp4_fallback_calls += 1
     out = F.linear(x, dequantize_mxfp4_rows(w, w_scale, x.dtype), bias)
     return silu_and_mul_fused(out) if fuse_silu_mul else out
 
 
-def _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows):
+def _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, mxfp4_rows="fallback"):
     global mxfp4_native_calls
     _mxfp4_check_x(x, w, w_scale)
     N = w.shape[0]
@@ -200,6 +214,12 @@ def _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, 
                                              current_stream_handle()), "gemv_near_pull_mxfp4")
         mxfp4_native_calls += 1
         return y
+    if mxfp4_rows == "native" and _mxfp4_native_rows(x, w, w_scale, rows):
+        y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
+        check(lib().skv_linear_rows_mxfp4(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), rows, N, K, 1 if fuse_silu_mul else 0,
+                                          current_stream_handle()), "linear_rows_mxfp4")
+        mxfp4_native_calls += 1
+        return y
     if not native:
         y = _mxfp4_linear_fallback(x, w, w_scale, bias, fuse_silu_mul)
         return y if out is None else out.copy_(y)
@@ -210,7 +230,8 @@ def _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, 
     return y
 
 
-def _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull):
+def _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
+                              mxfp4_rows="fallback"):
     global mxfp4_native_calls
     _mxfp4_check_x(x, w, w_scale)
     K, N = x.shape[-1], w.shape[0]
@@ -221,7 +242,7 @@ def _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_s
         raise ValueError("range_max: one token, hidden size 4096, N % 16 == 0, N <= 262,144, no fused SiLU")
     if not one_launch:
         h, hs = add_rmsnorm(x, residual, norm_w, eps)
-        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale)
+        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale, mxfp4_rows=mxfp4_rows)
     y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
     h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
     head = (ptr(w), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0)
@@ -280,7 +301,8 @@ def _fp8_linear_fallback(x, w, w_scale, bias, fuse_silu_mul):
 MAX_GEMV_ROWS = 32   # token rows served by the native kernels (1: GEMV, 2..32: small-M MFMA kernel); more -> F.linear
 
 
-def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None, w_scale=None, fp8_rows="fallback"):
+def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None, w_scale=None, fp8_rows="fallback",
+                  mxfp4_rows="fallback"):
     """F.linear for decode-time activations (x [..., K] with a handful of token rows): one token -> the native GEMV,
     2..MAX_GEMV_ROWS tokens -> the native small-M MFMA kernel (weights stream once); falls back to F.linear for more
     rows or shapes the kernels are not built for.  fuse_silu_mul: w = [gate; up] -> silu(gate.x) * (up.x).
@@ -293,12 +315,16 @@ def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None
     other multi-row shape still falls back.  One token row, near_pull and the default are unchanged.
     w uint8 [N, K / 2] with w_scale uint8 [N, K / 32] (quantize_mxfp4_rows): an MXFP4 pair - one contiguous token row with
     K % 32 == 0 and K >= 1024 takes the native MXFP4 GEMV (near_pull included), everything else the dequantising fallback;
-    fp8_rows is not read."""
+    fp8_rows is not read.
+    mxfp4_rows ("fallback" | "native"; read with an MXFP4 pair only): "native" sends 2..MAX_GEMV_ROWS contiguous token rows on
+    the GPU with K % 128 == 0 through skv_linear_rows_mxfp4 - the nibbles stream once, nothing is dequantised (DESIGN.md section
+    12.1); every other multi-row shape still falls back.  One token row, near_pull and the default are unchanged."""
     _fp8_rows_check(fp8_rows)
+    _mxfp4_rows_check(mxfp4_rows)
     K = x.shape[-1]
     rows = x.numel() // K
     if w.dtype == torch.uint8:          # an MXFP4 pair (fp8_rows does not apply to it)
-        return _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows)
+        return _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, mxfp4_rows)
     if w_scale is not None:
         return _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, fp8_rows)
     if near_pull is not None:
@@ -358,7 +384,7 @@ def range_max_supported(x_numel, K, N):
 
 
 def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=False, out=None, h_out=None, range_max=None,
-                       near_pull=None, w_scale=None, fp8_rows="fallback"):
+                       near_pull=None, w_scale=None, fp8_rows="fallback", mxfp4_rows="fallback"):
     """(h, y): h = x + residual (residual None -> h = x), y = linear(RMSNorm(h) * norm_w) for one token, one
     native launch when the hidden size is 4096; otherwise add_rmsnorm + linear_decode.  out / h_out: caller-owned
     result buffers (the eager decode paths reuse theirs instead of allocating per call).
@@ -368,12 +394,15 @@ def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=Fal
     stage the near misses of this step's selection ahead of the next step (skv_norm_gemv_near_pull_bf16); same y.
     w_scale (f32 [N]): w holds float8_e4m3fn bytes - the same one-launch paths with the FP8 kernels (same h, bit for bit);
     other shapes: add_rmsnorm + linear_decode(..., w_scale=, fp8_rows=) - fp8_rows as in linear_decode.
-    An MXFP4 pair (w uint8 [N, K / 2], w_scale uint8 [N, K / 32]) takes the same paths with the MXFP4 kernels."""
+    An MXFP4 pair (w uint8 [N, K / 2], w_scale uint8 [N, K / 32]) takes the same paths with the MXFP4 kernels; other shapes:
+    add_rmsnorm + linear_decode(..., w_scale=, mxfp4_rows=) - mxfp4_rows as in linear_decode."""
     _fp8_rows_check(fp8_rows)
+    _mxfp4_rows_check(mxfp4_rows)
     K = x.shape[-1]
     N = w.shape[0]
     if w.dtype == torch.uint8:          # an MXFP4 pair (fp8_rows does not apply to it)
-        return _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull)
+        return _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
+                                         mxfp4_rows)
     if w_scale is not None:
         return _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
                                        fp8_rows)
@@ -472,15 +501,16 @@ def qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_he
 
 
 def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads,
-                         kv_heads, q_override=None, w_scale=None, fp8_rows="fallback"):
+                         kv_heads, q_override=None, w_scale=None, fp8_rows="fallback", mxfp4_rows="fallback"):
     """(h, q) for ONE token of ONE sequence: h = x + residual, q = RoPE(split(linear(RMSNorm(h)))) [1, Hq, 1, D];
     rotated k and v are pushed into row row_idx of k_cache / v_cache [1, Hkv, rows, D].  One native launch when the
     hidden size is 4096 and bs == 1; otherwise norm_linear_decode + qkv_rope_update.
     w_scale (f32 [rows of wqkv]): wqkv holds float8_e4m3fn bytes - the same two paths with the FP8 kernels; fp8_rows as in
     linear_decode (the multi-row path's projection).  An MXFP4 pair (wqkv uint8 [N, K / 2], w_scale uint8 [N, K / 32]) takes
-    the same two paths with the MXFP4 kernels."""
+    the same two paths with the MXFP4 kernels; mxfp4_rows as in linear_decode (the multi-row path's projection)."""
     global fp8_native_calls, mxfp4_native_calls
     _fp8_rows_check(fp8_rows)
+    _mxfp4_rows_check(mxfp4_rows)
     K = x.shape[-1]
     D = k_cache.shape[-1]
     mx = wqkv.dtype == torch.uint8
@@ -490,7 +520,7 @@ def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row
         _fp8_check(wqkv, w_scale)
     if x.numel() != K or K != 4096 or not x.is_contiguous() or not wqkv.is_contiguous() or D != 128 \
             or (mx and not w_scale.is_contiguous()):
-        h, qkv = norm_linear_decode(x, residual, norm_w, eps, wqkv, bqkv, w_scale=w_scale, fp8_rows=fp8_rows)
+        h, qkv = norm_linear_decode(x, residual, norm_w, eps, wqkv, bqkv, w_scale=w_scale, fp8_rows=fp8_rows, mxfp4_rows=mxfp4_rows)
         return h, qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_heads, q_override)
     q = torch.empty(1, q_heads, 1, D, dtype=x.dtype, device=x.device)
     h = torch.empty_like(x) if residual is not None else x

@@ -8,7 +8,10 @@ fp8_e4m3); given explicitly it also appends the relative deviation of one probe 
 token, same synthetic queries, same context - a random-weight figure, not an accuracy measurement).
 --batch B (B > 1): the batched headline configuration (in-place layout, V in pinned host memory, eager decode_step - a captured
 graph at bs > 1 is not part of the FP8 rows work) as a triple over one context, measured one after the other: the bf16 model, the
-FP8 model with the dequantising fallback, the FP8 model with fp8_rows="native" (skv_linear_rows_fp8)."""
+FP8 model with the dequantising fallback, the FP8 model with fp8_rows="native" (skv_linear_rows_fp8).
+--weight-dtype mxfp4 --batch B: the same triple for MXFP4 weights - bf16, the MXFP4 model with the dequantising fallback, the
+MXFP4 model with mxfp4_rows="native" (skv_linear_rows_mxfp4); --mxfp4-rows {both,fallback,native} picks
+which of the two MXFP4 measurements run (the fallback dequantises every matrix on every step: it is the slow one)."""
 import argparse
 import os
 import sys
@@ -71,28 +74,34 @@ def run_eager(model, ctx, steps, warmup, seed=4242):
     return steps * model.batch_size / (time.perf_counter() - t0)
 
 
-def batched(a):
+def batched(a, wd="fp8_e4m3"):
     from shadowkv_amd import tensor_op
+    mx = wd == "mxfp4"
+    tag, attr = ("mxfp4", "mxfp4_rows") if mx else ("fp8", "fp8_rows")
+    modes = ("fallback", "native") if not mx or a.mxfp4_rows == "both" else (a.mxfp4_rows,)
+    calls = lambda: (getattr(tensor_op, tag + "_native_calls"), getattr(tensor_op, tag + "_fallback_calls"))
     ctx, dev = 122 * 1024, "cuda:0"
     model = llama.DecoderLM(cfg=llama.LLAMA_3_1_8B, batch_size=a.batch, max_length=ctx, device=dev, sparse_budget=2048, rank=160,
                             chunk_size=8, num_layers=a.layers, chunk_layout="inplace", overlap_attention=True,
                             max_new_tokens=max(1024, 8 * (a.warmup + a.steps) + 256))
     llama.build_synthetic_context(model, ctx, seed=4321)
     res = {"bf16": (run_eager(model, ctx, a.steps, a.warmup), model.weight_bytes(), 0, 0)}
-    model.quantize_weights()
+    model.quantize_weights(dtype=wd)
     torch.cuda.empty_cache()
-    for mode in ("fallback", "native"):
-        model.fp8_rows = mode
-        n0, f0 = tensor_op.fp8_native_calls, tensor_op.fp8_fallback_calls
+    for mode in modes:
+        setattr(model, attr, mode)
+        n0, f0 = calls()
         tps = run_eager(model, ctx, a.steps, a.warmup)
-        res["fp8 " + mode] = (tps, model.weight_bytes(), tensor_op.fp8_native_calls - n0, tensor_op.fp8_fallback_calls - f0)
+        res[f"{tag} {mode}"] = (tps, model.weight_bytes(), calls()[0] - n0, calls()[1] - f0)
     lines = [f"# tools/fp8_e2e.py --batch {a.batch} on {torch.cuda.get_device_name(0)}: 122 K synthetic context, budget 2048, in-place + "
              f"overlap_attention, V in pinned host memory, eager decode_step, {model.num_layers} layers, {a.steps} steps after {a.warmup} warm-up steps"]
     for k, (tps, nbytes, nat, fb) in res.items():
-        lines.append(f"bs {a.batch:2d} {k:<13} {tps:8.2f} tokens/s  weights {nbytes / 1e9:6.2f} GB  native FP8 launches {nat}  "
+        lines.append(f"bs {a.batch:2d} {k:<14} {tps:8.2f} tokens/s  weights {nbytes / 1e9:6.2f} GB  native {'MXFP4' if mx else 'FP8'} launches {nat}  "
                      f"dequantising fallbacks {fb}")
-    lines.append(f"bs {a.batch:2d} tokens/s ratios: fp8 native : bf16 {res['fp8 native'][0] / res['bf16'][0]:.3f}   "
-                 f"fp8 native : fp8 fallback {res['fp8 native'][0] / res['fp8 fallback'][0]:.3f}")
+    ratios = [f"{tag} {m} : bf16 {res[f'{tag} {m}'][0] / res['bf16'][0]:.3f}" for m in modes]
+    if len(modes) == 2:
+        ratios.append(f"{tag} native : {tag} fallback {res[f'{tag} native'][0] / res[f'{tag} fallback'][0]:.3f}")
+    lines.append(f"bs {a.batch:2d} tokens/s ratios: " + "   ".join(ratios))
     return lines
 
 
@@ -104,12 +113,11 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--weight-dtype", dest="weight_dtype", choices=("fp8_e4m3", "mxfp4"), default=None)
+    ap.add_argument("--mxfp4-rows", dest="mxfp4_rows", choices=("both", "fallback", "native"), default="both")
     a = ap.parse_args()
     wd = a.weight_dtype or "fp8_e4m3"
-    if a.batch > 1 and wd != "fp8_e4m3":
-        ap.error("--batch > 1 measures the FP8 rows paths: --weight-dtype applies to bs 1")
     if a.batch > 1:
-        lines = batched(a)
+        lines = batched(a, wd)
         print("\n".join(lines))
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
