@@ -410,6 +410,35 @@ SKV_EXPORT int skv_select_chunks_fused_kv_proj(const void* q, const void* landma
                             float alpha, void* select_state, void* early_state, const void* v_host, long long host_block_stride,
                             int n_chunks, int early_max, float margin, const skv_kv_proj_t* kv_proj, skv_stream_t stream);
 
+/* ---- FP8 (e4m3) landmark table -------------------------------------------------------------------
+ * Each entry is its bf16 namesake with `landmarks` the OCP e4m3fn byte table [blocks][n][128] (row-major) and lm_scale f32
+ * [blocks][n] right behind it: one power-of-two scale per landmark row, as skv_quantize_v_rows writes them (tokens = n).
+ * The scan computes on bf16(lm_scale * e4m3(byte)), which is exact, so every output (logits, keys, partials, early-fetch flags,
+ * and with them selection, miss lists, cnts, slot_age, select state, staging lists) equals, bit for bit, what the bf16 entry
+ * writes when handed the dequantised table.  A null table or a null scale: SKV_ERR_ARG, before any HIP call; a shape the
+ * bf16 entry refuses gets the same code.  The non-fused *_early entries have no FP8 form. */
+SKV_EXPORT int skv_score_landmarks_fp8(const void* q, const void* landmarks, const float* lm_scale, void* logits, float* part_max,
+                        float* part_sum, int blocks, int groups, int n_landmarks, float alpha, skv_stream_t stream);
+SKV_EXPORT int skv_score_landmarks_fused_fp8(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                              void* workspace, int blocks, int groups, int n_landmarks, float alpha, void* select_state,
+                              void* early_state, int n_chunks, int early_max, skv_stream_t stream);   /* measurement, as its namesake */
+SKV_EXPORT int skv_select_chunks_fp8(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                      int64_t* cached_pos_ids, int32_t* offsets, int32_t* cnts, void* workspace, void* softmax_out,
+                      int64_t* selected_out, int blocks, int groups, int n_landmarks, int select_sets, float alpha,
+                      skv_stream_t stream);
+SKV_EXPORT int skv_select_chunks_inplace_fp8(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                              int64_t* cached_pos_ids, int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts,
+                              void* workspace, void* softmax_out, int64_t* selected_out, int blocks, int groups,
+                              int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age, float alpha,
+                              skv_stream_t stream);
+/* kv_proj NULL: skv_select_chunks_fused; non-NULL: skv_select_chunks_fused_kv_proj */
+SKV_EXPORT int skv_select_chunks_fused_fp8(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                            int64_t* cached_pos_ids, int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts, void* workspace,
+                            int64_t* selected_out, int blocks, int groups, int n_landmarks, int select_sets, int resident_sets,
+                            int32_t* slot_age, float alpha, void* select_state, void* early_state, const void* v_host,
+                            long long host_block_stride, int n_chunks, int early_max, float margin,
+                            const skv_kv_proj_t* kv_proj, skv_stream_t stream);
+
 /* ---- speculative early V fetch (in-place layout) -------------------------------------------------------------------
  * Which chunks a step will MISS is predictable as soon as the scan has produced the logits: a landmark slot whose logit
  * reaches the previous step's k-th value (in logit space, per query head) and whose chunk is not resident.  With an early

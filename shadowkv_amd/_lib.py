@@ -112,6 +112,13 @@ _SIGS = {
     "skv_land_chunks_fp8": (c_int, [c_p] * 5 + [c_ll] * 3 + [c_int] * 2 + [c_p, c_ll, c_p]),
     "skv_fetch_kv_fp8": (c_int, [c_p] * 11 + [c_int] * 7 + [c_ll] * 4 + [c_int] * 2 + [c_ll, c_p, c_ll, c_p]),
     "skv_fetch_kv_inplace_fp8": (c_int, [c_p] * 9 + [c_int] * 7 + [c_ll] * 4 + [c_int] * 2 + [c_ll, c_p, c_ll, c_p]),
+    # FP8 (e4m3) landmark table: the bf16 entries with the f32 row scales (lm_scale) behind `landmarks`
+    "skv_score_landmarks_fp8": (c_int, [c_p] * 6 + [c_int] * 3 + [c_f, c_p]),
+    "skv_score_landmarks_fused_fp8": (c_int, [c_p] * 5 + [c_int] * 3 + [c_f, c_p, c_p, c_int, c_int, c_p]),
+    "skv_select_chunks_fp8": (c_int, [c_p] * 10 + [c_int] * 4 + [c_f, c_p]),
+    "skv_select_chunks_inplace_fp8": (c_int, [c_p] * 11 + [c_int] * 5 + [c_p, c_f, c_p]),
+    "skv_select_chunks_fused_fp8": (c_int, [c_p] * 10 + [c_int] * 5 + [c_p, c_f] + [c_p, c_p, c_p, c_ll, c_int, c_int, c_f,
+                                            ctypes.POINTER(KvProjDesc), c_p]),
     "skv_chunk_stats": (c_int, [c_p, c_ll] + [c_int] * 4 + [c_p] * 3),
     "skv_host_alloc": (c_int, [ctypes.POINTER(c_p), c_sz]),
     "skv_host_free": (c_int, [c_p]),

@@ -11,7 +11,7 @@
 // launchers (defined in the kernel files)
 int skv_launch_score(const void* q, const void* lm, void* D, float* pmax, float* psum, int B, int G, int N,
                      float alpha, hipStream_t st, const EarlyHooks* hooks = nullptr, const FusedSel* fused = nullptr,
-                     const KvProj* kv_proj = nullptr);
+                     const KvProj* kv_proj = nullptr, const float* lm_scale = nullptr /* non-null: lm is an e4m3 table */);
 int skv_launch_softmax_final_apply(const void* D, float* pmax, float* psum, void* P, int B, int m, int N,
                                    hipStream_t st);
 int skv_launch_normalize_groupmax(const void* D, const float* pmax, const float* psum, void* P, void* score,
@@ -270,14 +270,16 @@ size_t skv_select_workspace_bytes(int blocks, int groups, int n_landmarks) {
     return carve_select_ws(nullptr, blocks, groups, n_landmarks).total;
 }
 
-int skv_select_chunks(const void* q, const void* landmarks, const int64_t* landmark_idx, int64_t* cached_pos_ids,
-                      int32_t* offsets, int32_t* cnts, void* workspace, void* softmax_out, int64_t* selected_out,
-                      int blocks, int groups, int n_landmarks, int select_sets, float alpha, skv_stream_t stream) {
+// (every selection entry below has an FP8-landmark form, DESIGN.md section 13: lm_scale non-null = `landmarks` is the e4m3 table)
+static int select_chunks_impl(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                              int64_t* cached_pos_ids, int32_t* offsets, int32_t* cnts, void* workspace, void* softmax_out,
+                              int64_t* selected_out, int blocks, int groups, int n_landmarks, int select_sets, float alpha,
+                              skv_stream_t stream) {
     if (!q || !landmarks || !cached_pos_ids || !offsets || !cnts || !workspace) return SKV_ERR_ARG;
     if (blocks < 1 || n_landmarks < select_sets || select_sets < 1) return SKV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     SelectWs w = carve_select_ws(workspace, blocks, groups, n_landmarks);
-    int rc = skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, st);
+    int rc = skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, st, nullptr, nullptr, nullptr, lm_scale);
     if (rc != SKV_OK) return rc;
     rc = skv_launch_normalize_groupmax(w.D, w.pmax, w.psum, softmax_out, w.score, w.score_stride, blocks, groups,
                                        n_landmarks, st);
@@ -286,16 +288,32 @@ int skv_select_chunks(const void* q, const void* landmarks, const int64_t* landm
                                           selected_out, nullptr, blocks, n_landmarks, select_sets, st));
 }
 
-int skv_select_chunks_inplace(const void* q, const void* landmarks, const int64_t* landmark_idx,
-                              int64_t* cached_pos_ids, int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts,
-                              void* workspace, void* softmax_out, int64_t* selected_out, int blocks, int groups,
-                              int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age, float alpha,
-                              skv_stream_t stream) {
+int skv_select_chunks(const void* q, const void* landmarks, const int64_t* landmark_idx, int64_t* cached_pos_ids,
+                      int32_t* offsets, int32_t* cnts, void* workspace, void* softmax_out, int64_t* selected_out,
+                      int blocks, int groups, int n_landmarks, int select_sets, float alpha, skv_stream_t stream) {
+    return select_chunks_impl(q, landmarks, nullptr, landmark_idx, cached_pos_ids, offsets, cnts, workspace, softmax_out, selected_out,
+                              blocks, groups, n_landmarks, select_sets, alpha, stream);
+}
+
+int skv_select_chunks_fp8(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                          int64_t* cached_pos_ids, int32_t* offsets, int32_t* cnts, void* workspace, void* softmax_out,
+                          int64_t* selected_out, int blocks, int groups, int n_landmarks, int select_sets, float alpha,
+                          skv_stream_t stream) {
+    if (!landmarks || !lm_scale) return SKV_ERR_ARG;
+    return select_chunks_impl(q, landmarks, lm_scale, landmark_idx, cached_pos_ids, offsets, cnts, workspace, softmax_out, selected_out,
+                              blocks, groups, n_landmarks, select_sets, alpha, stream);
+}
+
+static int select_chunks_inplace_impl(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                                      int64_t* cached_pos_ids, int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts,
+                                      void* workspace, void* softmax_out, int64_t* selected_out, int blocks, int groups,
+                                      int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age, float alpha,
+                                      skv_stream_t stream) {
     if (!q || !landmarks || !cached_pos_ids || !miss_ids || !dst_slots || !cnts || !workspace) return SKV_ERR_ARG;
     if (blocks < 1 || n_landmarks < select_sets || select_sets < 1 || resident_sets < select_sets) return SKV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     SelectWs w = carve_select_ws(workspace, blocks, groups, n_landmarks);
-    int rc = skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, st);
+    int rc = skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, st, nullptr, nullptr, nullptr, lm_scale);
     if (rc != SKV_OK) return rc;
     rc = skv_launch_normalize_groupmax(w.D, w.pmax, w.psum, softmax_out, w.score, w.score_stride, blocks, groups,
                                        n_landmarks, st);
@@ -303,6 +321,27 @@ int skv_select_chunks_inplace(const void* q, const void* landmarks, const int64_
     return finish(skv_launch_topk_resident(w.score, w.score_stride, landmark_idx, nullptr, cached_pos_ids, miss_ids, cnts,
                                            selected_out, dst_slots, blocks, n_landmarks, select_sets, resident_sets,
                                            slot_age, st));
+}
+
+int skv_select_chunks_inplace(const void* q, const void* landmarks, const int64_t* landmark_idx,
+                              int64_t* cached_pos_ids, int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts,
+                              void* workspace, void* softmax_out, int64_t* selected_out, int blocks, int groups,
+                              int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age, float alpha,
+                              skv_stream_t stream) {
+    return select_chunks_inplace_impl(q, landmarks, nullptr, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace,
+                                      softmax_out, selected_out, blocks, groups, n_landmarks, select_sets, resident_sets, slot_age,
+                                      alpha, stream);
+}
+
+int skv_select_chunks_inplace_fp8(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                                  int64_t* cached_pos_ids, int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts,
+                                  void* workspace, void* softmax_out, int64_t* selected_out, int blocks, int groups,
+                                  int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age, float alpha,
+                                  skv_stream_t stream) {
+    if (!landmarks || !lm_scale) return SKV_ERR_ARG;
+    return select_chunks_inplace_impl(q, landmarks, lm_scale, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace,
+                                      softmax_out, selected_out, blocks, groups, n_landmarks, select_sets, resident_sets, slot_age,
+                                      alpha, stream);
 }
 
 // ---- speculative early V fetch (skv_early.hip) -------------------------------------------------------------------
@@ -410,7 +449,7 @@ static int kv_proj_of(KvProj& kp, const skv_kv_proj_t* d) {
     return SKV_OK;
 }
 
-static int select_chunks_fused_impl(const void* q, const void* landmarks, const int64_t* landmark_idx, int64_t* cached_pos_ids,
+static int select_chunks_fused_impl(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx, int64_t* cached_pos_ids,
                             int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts, void* workspace, int64_t* selected_out,
                             int blocks, int groups, int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age,
                             float alpha, void* select_state, void* early_state, const void* v_host, long long host_block_stride,
@@ -444,7 +483,7 @@ static int select_chunks_fused_impl(const void* q, const void* landmarks, const 
         if (rc != SKV_OK) return rc;
         (kv_proj->placement == SKV_KV_PROJ_IN_SCAN ? in_scan : in_topk) = &kp;
     }
-    int rc = skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, st, hooks, &fs, in_scan);
+    int rc = skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, st, hooks, &fs, in_scan, lm_scale);
     if (rc != SKV_OK) return rc;
     return finish(skv_launch_topk_resident(w.score, w.score_stride, landmark_idx, nullptr, cached_pos_ids, miss_ids, cnts,
                                            selected_out, dst_slots, blocks, n_landmarks, select_sets, resident_sets, slot_age, st,
@@ -456,7 +495,7 @@ int skv_select_chunks_fused(const void* q, const void* landmarks, const int64_t*
                             int blocks, int groups, int n_landmarks, int select_sets, int resident_sets, int32_t* slot_age,
                             float alpha, void* select_state, void* early_state, const void* v_host, long long host_block_stride,
                             int n_chunks, int early_max, float margin, skv_stream_t stream) {
-    return select_chunks_fused_impl(q, landmarks, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace, selected_out,
+    return select_chunks_fused_impl(q, landmarks, nullptr, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace, selected_out,
                                     blocks, groups, n_landmarks, select_sets, resident_sets, slot_age, alpha, select_state,
                                     early_state, v_host, host_block_stride, n_chunks, early_max, margin, nullptr, stream);
 }
@@ -467,9 +506,21 @@ int skv_select_chunks_fused_kv_proj(const void* q, const void* landmarks, const 
                                     float alpha, void* select_state, void* early_state, const void* v_host,
                                     long long host_block_stride, int n_chunks, int early_max, float margin,
                                     const skv_kv_proj_t* kv_proj, skv_stream_t stream) {
-    return select_chunks_fused_impl(q, landmarks, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace, selected_out,
+    return select_chunks_fused_impl(q, landmarks, nullptr, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace, selected_out,
                                     blocks, groups, n_landmarks, select_sets, resident_sets, slot_age, alpha, select_state,
                                     early_state, v_host, host_block_stride, n_chunks, early_max, margin, kv_proj, stream);
+}
+
+int skv_select_chunks_fused_fp8(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                                int64_t* cached_pos_ids, int32_t* miss_ids, int32_t* dst_slots, int32_t* cnts, void* workspace,
+                                int64_t* selected_out, int blocks, int groups, int n_landmarks, int select_sets, int resident_sets,
+                                int32_t* slot_age, float alpha, void* select_state, void* early_state, const void* v_host,
+                                long long host_block_stride, int n_chunks, int early_max, float margin,
+                                const skv_kv_proj_t* kv_proj, skv_stream_t stream) {
+    if (!landmarks || !lm_scale) return SKV_ERR_ARG;
+    return select_chunks_fused_impl(q, landmarks, lm_scale, landmark_idx, cached_pos_ids, miss_ids, dst_slots, cnts, workspace,
+                                    selected_out, blocks, groups, n_landmarks, select_sets, resident_sets, slot_age, alpha,
+                                    select_state, early_state, v_host, host_block_stride, n_chunks, early_max, margin, kv_proj, stream);
 }
 
 // reference slot order (skv_select_chunks / skv_fetch_kv) with the early fetch
@@ -535,6 +586,13 @@ int skv_score_landmarks(const void* q, const void* landmarks, void* logits, floa
                                    (hipStream_t)stream));
 }
 
+int skv_score_landmarks_fp8(const void* q, const void* landmarks, const float* lm_scale, void* logits, float* part_max,
+                            float* part_sum, int blocks, int groups, int n_landmarks, float alpha, skv_stream_t stream) {
+    if (!q || !landmarks || !lm_scale || !logits || !part_max || !part_sum || blocks < 1 || n_landmarks < 1) return SKV_ERR_ARG;
+    return finish(skv_launch_score(q, landmarks, logits, part_max, part_sum, blocks, groups, n_landmarks, alpha,
+                                   (hipStream_t)stream, nullptr, nullptr, nullptr, lm_scale));
+}
+
 int skv_score_landmarks_early(const void* q, const void* landmarks, const int64_t* landmark_idx, void* logits, float* part_max,
                               float* part_sum, int blocks, int groups, int n_landmarks, float alpha, void* early_state,
                               int n_chunks, int early_max, skv_stream_t stream) {
@@ -549,9 +607,9 @@ int skv_score_landmarks_early(const void* q, const void* landmarks, const int64_
 }
 
 /* the scan launch exactly as skv_select_chunks_fused issues it (measurement: bench.py's roofline of the dominant kernel) */
-int skv_score_landmarks_fused(const void* q, const void* landmarks, const int64_t* landmark_idx, void* workspace, int blocks,
-                              int groups, int n_landmarks, float alpha, void* select_state, void* early_state, int n_chunks,
-                              int early_max, skv_stream_t stream) {
+static int score_landmarks_fused_impl(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                                      void* workspace, int blocks, int groups, int n_landmarks, float alpha, void* select_state,
+                                      void* early_state, int n_chunks, int early_max, skv_stream_t stream) {
     if (!q || !landmarks || !workspace || !select_state || blocks < 1 || n_landmarks < 1) return SKV_ERR_ARG;
     if (!skv_fused_select_supported(groups, n_landmarks, 1)) return SKV_ERR_UNSUPPORTED;
     SelectWs w = carve_select_ws(workspace, blocks, groups, n_landmarks);
@@ -564,7 +622,22 @@ int skv_score_landmarks_fused(const void* q, const void* landmarks, const int64_
         eh.T = (n_landmarks + 255) / 256; eh.N = n_landmarks; eh.n_chunks = n_chunks; eh.E = early_max;
     }
     return finish(skv_launch_score(q, landmarks, w.D, w.pmax, w.psum, blocks, groups, n_landmarks, alpha, (hipStream_t)stream,
-                                   early_state ? &eh : nullptr, &fs));
+                                   early_state ? &eh : nullptr, &fs, nullptr, lm_scale));
+}
+
+int skv_score_landmarks_fused(const void* q, const void* landmarks, const int64_t* landmark_idx, void* workspace, int blocks,
+                              int groups, int n_landmarks, float alpha, void* select_state, void* early_state, int n_chunks,
+                              int early_max, skv_stream_t stream) {
+    return score_landmarks_fused_impl(q, landmarks, nullptr, landmark_idx, workspace, blocks, groups, n_landmarks, alpha, select_state,
+                                      early_state, n_chunks, early_max, stream);
+}
+
+int skv_score_landmarks_fused_fp8(const void* q, const void* landmarks, const float* lm_scale, const int64_t* landmark_idx,
+                                  void* workspace, int blocks, int groups, int n_landmarks, float alpha, void* select_state,
+                                  void* early_state, int n_chunks, int early_max, skv_stream_t stream) {
+    if (!landmarks || !lm_scale) return SKV_ERR_ARG;
+    return score_landmarks_fused_impl(q, landmarks, lm_scale, landmark_idx, workspace, blocks, groups, n_landmarks, alpha, select_state,
+                                      early_state, n_chunks, early_max, stream);
 }
 
 int skv_rebuild_keys(const void* U, const void* SV, const void* cos_sin, const int64_t* chunk_ids,

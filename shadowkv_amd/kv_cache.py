@@ -14,6 +14,7 @@ State (per layer l, batch b, KV head h; D = head_dim, C = chunk_size, S = sparse
         rows [sparse_end, buf_len)         tokens generated so far
   U [L, bs, seq, r], SV [L, bs, kv, D, r]   rank-r factorisation of the pre-RoPE keys (r-contiguous)
   k_landmark [L, bs, kv, N, D], k_landmark_idx int64 [L, bs, kv, N]   chunk means + their chunk ids
+        landmark_dtype="fp8_e4m3": float8_e4m3fn, 128-byte rows, + k_landmark_scale f32 [L, bs, kv, N]
   position_ids int64 [L, bs, kv, R], offsets int32 [bs*kv*S], cnts int32 [bs*kv], signals int32 [bs*kv]
 
 MI355X-first differences that do not change results:
@@ -147,11 +148,18 @@ def gram_factorize(k, rank):
 class ShadowKVCache_CPU:
     def __init__(self, config, batch_size=1, max_length=32 * 1024, device="cuda:0", dtype=torch.bfloat16,
                  sparse_budget=2048, chunk_size=8, rank=160, svd_mode="auto", v_offload=True, resident_sets=None,
-                 v_dtype="bf16"):
+                 v_dtype="bf16", landmark_dtype="bf16"):
         if dtype != torch.bfloat16:
             raise ValueError("ShadowKVCache_CPU supports bfloat16 only (as the reference's kernels do)")
         if v_dtype not in tensor_op.V_DTYPES:           # (before anything is allocated)
             raise ValueError(f"v_dtype must be one of {tensor_op.V_DTYPES}, got {v_dtype!r}")
+        if landmark_dtype not in tensor_op.LANDMARK_DTYPES:
+            raise ValueError(f"landmark_dtype must be one of {tensor_op.LANDMARK_DTYPES}, got {landmark_dtype!r}")
+        # "fp8_e4m3" (DESIGN.md section 13): k_landmark holds e4m3 bytes with one f32 power-of-two scale per landmark row
+        # (k_landmark_scale, the V table's quantisation rule) - half the bytes of the decode scan, the one HBM-bound kernel of the
+        # path.  Only the landmark table is quantised; the selection is the exact selection over the rounded landmarks.
+        self.landmark_dtype = landmark_dtype
+        self.k_landmark_scale = None
         # "fp8_e4m3" (DESIGN.md section 11): the chunked V table holds e4m3 bytes (1 KiB rows) with one f32 power-of-two scale
         # per token row in HBM (v_scale) - half the PCIe bytes per miss and half the pinned memory.  Only the table is
         # quantised; every V row of the sparse region equals dequant(table row of the chunk in that slot) at all times.
@@ -306,6 +314,7 @@ class ShadowKVCache_CPU:
         self.k_cache_buffer.zero_()
         self.v_cache_buffer.zero_()
         self.k_landmark = None
+        self.k_landmark_scale = None
         self.k_landmark_idx = None
         self.U = None
         self.SV = None
@@ -383,21 +392,47 @@ class ShadowKVCache_CPU:
     def register_k_landmark(self, k_landmark, k_landmark_idx, layer_idx):
         n = k_landmark.shape[-2]
         bsz = k_landmark.shape[0]
+        fp8 = self.landmark_dtype == "fp8_e4m3"
+        if fp8 and self.head_dim != 128:
+            raise ValueError("landmark_dtype='fp8_e4m3' is built for head_dim 128")
         if layer_idx == 0 and self.prefilled_batch == 0:
-            self.k_landmark = torch.zeros(self.num_layers, self.batch_size, self.num_key_value_heads, n, self.head_dim,
-                                          device=self.device, dtype=self.dtype)
+            shape = (self.num_layers, self.batch_size, self.num_key_value_heads, n, self.head_dim)
+            if fp8:
+                self.k_landmark = torch.zeros(shape, device=self.device, dtype=torch.uint8).view(torch.float8_e4m3fn)
+                self.k_landmark_scale = torch.ones(shape[:-1], device=self.device, dtype=torch.float32)
+            else:
+                self.k_landmark = torch.zeros(shape, device=self.device, dtype=self.dtype)
             self.k_landmark_idx = torch.zeros(self.num_layers, self.batch_size, self.num_key_value_heads, n,
                                               device=self.device, dtype=torch.long)
         b0 = self.prefilled_batch
-        self.k_landmark[layer_idx][b0:b0 + bsz].copy_(k_landmark)
+        if fp8:
+            # the bf16 means, quantised by the V table's quantiser (same bytes from the native pass and the torch mirror)
+            table, scale = self.k_landmark[layer_idx][b0:b0 + bsz], self.k_landmark_scale[layer_idx][b0:b0 + bsz]
+            means = k_landmark.to(self.dtype)
+            if means.is_cuda:
+                tensor_op.quantize_v_rows(means, table.view(bsz, -1, n * self.head_dim), scale)   # straight into the table
+            else:
+                lm8, sc = tensor_op.quantize_v_rows_torch(means)
+                table.view(torch.uint8).copy_(lm8.view(torch.uint8))
+                scale.copy_(sc)
+        else:
+            self.k_landmark[layer_idx][b0:b0 + bsz].copy_(k_landmark)
         self.k_landmark_idx[layer_idx][b0:b0 + bsz].copy_(k_landmark_idx)
+
+    def landmarks_bf16(self, layer_idx, b0=0, bsz=None):
+        """The landmark rows the scan scores, as bf16 [bsz, kv, N, D]: the table itself, or dequant(FP8 table) (exact)."""
+        b1 = self.batch_size if bsz is None else b0 + bsz
+        lm = self.k_landmark[layer_idx][b0:b1]
+        if self.k_landmark_scale is None:
+            return lm
+        return tensor_op.dequantize_v_rows(lm, self.k_landmark_scale[layer_idx][b0:b1], self.dtype)
 
     def _score_landmarks_torch(self, layer_idx, b0, bsz, last_q):
         """Initial selection at prefill time, in torch ops exactly as the reference does it
         (kv_cache.py:926-945): einsum / sqrt(128) -> f32 softmax -> bf16 -> max over the group -> topk."""
         kv, G, D = self.num_key_value_heads, self.num_key_value_groups, self.head_dim
         attn = torch.einsum("bhgd,bhcd->bhgc", last_q.view(-1, kv, G, D),
-                            self.k_landmark[layer_idx][b0:b0 + bsz].to(last_q.device)) / math.sqrt(128)
+                            self.landmarks_bf16(layer_idx, b0, bsz).to(last_q.device)) / math.sqrt(128)
         attn = torch.nn.functional.softmax(attn, dim=-1, dtype=torch.float32).to(self.dtype)
         attn, _ = torch.max(attn, dim=-2)
         top = torch.topk(attn, k=self.select_sets, dim=-1).indices
@@ -504,6 +539,10 @@ class ShadowKVCache_CPU:
         if self.v_scale is not None:
             raise RuntimeError(f"{what} is not available with v_dtype='fp8_e4m3': {why}")
 
+    def _refuse_fp8_landmarks(self, what, why):
+        if self.landmark_dtype != "bf16":
+            raise RuntimeError(f"{what} is not available with landmark_dtype='fp8_e4m3': {why}")
+
     def _land_v(self, lv, what):
         """The V landing launch of the reference layout (moved hits from the staging buffer, misses from the table)."""
         vhost, vbuf = lv.vhost, lv.vbuf
@@ -516,13 +555,13 @@ class ShadowKVCache_CPU:
 
     # ------------------------------------------------------------------ decode (native)
     class _LayerViews:
-        __slots__ = ("kbuf", "vbuf", "vhost", "vscale", "lm", "lm_idx", "pos", "U", "SV", "cnts", "age")
+        __slots__ = ("kbuf", "vbuf", "vhost", "vscale", "lm", "lmscale", "lm_idx", "pos", "U", "SV", "cnts", "age")
 
     def _layer(self, l):
         """Per-layer views of the state tensors, built once (indexing a tensor makes a new view object every time: ~2 us
         each, a dozen per layer and step on the eager paths); rebuilt when a parent tensor is replaced."""
         key = (self.k_cache_buffer, self.v_cache_buffer, self.v_cache_cpu, self.k_landmark, self.k_landmark_idx,
-               self.position_ids, self.U, self.SV)
+               self.position_ids, self.U, self.SV, self.k_landmark_scale)
         old = getattr(self, "_lv_key", None)
         if old is None or any(a is not b for a, b in zip(old, key)):        # (the parents themselves are held: no id reuse)
             self._lv = []
@@ -532,6 +571,7 @@ class ShadowKVCache_CPU:
                 v.lm, v.lm_idx, v.pos = self.k_landmark[i], self.k_landmark_idx[i], self.position_ids[i]
                 v.U, v.SV, v.cnts, v.age = self.U[i], self.SV[i], self._cnts_layers[i], self._slot_age[i]
                 v.vscale = None if self.v_scale is None else self.v_scale[i]
+                v.lmscale = None if self.k_landmark_scale is None else self.k_landmark_scale[i]
                 self._lv.append(v)
             self._lv_key = key
         return self._lv[l]
@@ -594,14 +634,20 @@ class ShadowKVCache_CPU:
         G, S, R = self.num_key_value_groups, self.select_sets, self.resident_sets
         if inplace and self._dst_slots is None:
             self._dst_slots = torch.zeros_like(self.offsets)
+        # FP8 landmark table: the *_fp8 entries - their bf16 namesakes with the row scales behind the table
+        lm_args = (ptr(lm),) if lv.lmscale is None else (ptr(lm), ptr(lv.lmscale))
+        fp8 = lv.lmscale is not None
         if self.fused_select and self._sel_state is not None and L.skv_select_fused_supported(G, n, S):
-            sel_args = (ptr(q), ptr(lm), ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets),
+            sel_args = (ptr(q), *lm_args, ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets),
                         ptr(self._dst_slots) if inplace else 0, ptr(self.cnts), ptr(self._select_ws), 0,
                         self.block_num, G, n, S, R if inplace else S, ptr(lv.age) if inplace else 0, alpha,
                         ptr(self._sel_state[layer_idx]), 0 if ea is None else ptr(ea["states"][layer_idx]),
                         ptr(vhost), vhost.stride(1), 0 if ea is None else ea["n_chunks"],
                         0 if ea is None else ea["E"], 0.0 if ea is None else ea["margin"])
-            if kv_proj is not None:      # the new token's K / V row is computed by extra workgroups of one of the two launches
+            if fp8:
+                check(L.skv_select_chunks_fused_fp8(*sel_args, None if kv_proj is None else ctypes.byref(kv_proj), st),
+                      "select_chunks_fused_fp8")
+            elif kv_proj is not None:    # the new token's K / V row is computed by extra workgroups of one of the two launches
                 check(L.skv_select_chunks_fused_kv_proj(*sel_args, ctypes.byref(kv_proj), st), "select_chunks_fused_kv_proj")
             else:
                 check(L.skv_select_chunks_fused(*sel_args, st), "select_chunks_fused")
@@ -609,12 +655,17 @@ class ShadowKVCache_CPU:
             return ea is not None
         if kv_proj is not None:
             raise RuntimeError("the k/v projection role rides in the fused selection launches only (kv_proj_role_supported)")
+        if fp8 and ea is not None:
+            raise RuntimeError("early fetch with landmark_dtype='fp8_e4m3' rides in the fused selection launches only "
+                               "(early_fetch_supported)")
         if inplace:
-            sel_args = (ptr(q), ptr(lm), ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets), ptr(self._dst_slots), ptr(self.cnts),
+            sel_args = (ptr(q), *lm_args, ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets), ptr(self._dst_slots), ptr(self.cnts),
                         ptr(self._select_ws), 0, 0, self.block_num, G, n, S, R, ptr(lv.age), alpha)
             if ea is not None:
                 check(L.skv_select_chunks_inplace_early(*sel_args, ptr(ea["states"][layer_idx]), ptr(vhost), vhost.stride(1),
                                                         ea["n_chunks"], ea["E"], ea["margin"], st), "select_chunks_inplace_early")
+            elif fp8:
+                check(L.skv_select_chunks_inplace_fp8(*sel_args, st), "select_chunks_inplace_fp8")
             else:
                 check(L.skv_select_chunks_inplace(*sel_args, st), "select_chunks_inplace")
             return ea is not None
@@ -624,8 +675,9 @@ class ShadowKVCache_CPU:
                                             ptr(vhost), vhost.stride(1), ea["n_chunks"], ea["E"], ea["margin"], st),
                   "get_retrieval_position_ids (early)")
             return True
-        check(L.skv_select_chunks(ptr(q), ptr(lm), ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets), ptr(self.cnts),
-                                  ptr(self._select_ws), 0, 0, self.block_num, G, n, S, alpha, st), "get_retrieval_position_ids")
+        sel_args = (ptr(q), *lm_args, ptr(lv.lm_idx), ptr(lv.pos), ptr(self.offsets), ptr(self.cnts), ptr(self._select_ws), 0, 0,
+                    self.block_num, G, n, S, alpha, st)
+        check((L.skv_select_chunks_fp8 if fp8 else L.skv_select_chunks)(*sel_args), "get_retrieval_position_ids")
         return False
 
     def _reference_layout_only(self, what):
@@ -698,6 +750,7 @@ class ShadowKVCache_CPU:
             self.sum = torch.zeros(bs * kv, G, (n + 255) // 256, device=self.device, dtype=torch.float32)
 
     def _ref_guard(self, what):
+        self._refuse_fp8_landmarks(f"{what} with reference_calls=True", "the reference's twelve-name API scores a bf16 table")
         self._refuse_fp8_v(f"{what} with reference_calls=True", "the reference's twelve-name API moves bf16 rows")
         if self.resident_sets != self.select_sets or self.inplace_methods or self.lazy_value_fetch:
             raise RuntimeError(f"{what}: reference_calls reproduces the reference's launch sequence, which has neither a larger "
@@ -868,8 +921,13 @@ class ShadowKVCache_CPU:
     def early_fetch_supported(self):
         """Shapes the early-fetch roles are built for (csrc/skv_early.h): <= 65,536 landmarks and <= 1,024 resident slots per
         head, V table in pinned host memory, bf16 (the staging buffer and the roles that fill and read it move 2 KiB rows)."""
-        return (self.v_scale is None and self.k_landmark is not None and self.k_landmark.shape[-2] <= 65536 and self.resident_sets <= 1024
-                and self.v_cache_cpu is not None and self.v_cache_cpu.is_pinned())
+        if not (self.v_scale is None and self.k_landmark is not None and self.k_landmark.shape[-2] <= 65536 and self.resident_sets <= 1024
+                and self.v_cache_cpu is not None and self.v_cache_cpu.is_pinned()):
+            return False
+        if self.landmark_dtype != "bf16":    # FP8 landmarks: the list role rides in the fused top-k launch only (no *_early entries)
+            return bool(self.fused_select and lib().skv_select_fused_supported(self.num_key_value_groups, self.k_landmark.shape[-2],
+                                                                                self.select_sets))
+        return True
 
     def _early_state(self):
         """The early-fetch state, or None when it is off.  The state is carved for ONE prompt's landmark count, chunk count

@@ -135,13 +135,17 @@ class DecoderLM:
                  attn_mode="shadowkv_cpu", sparse_budget=2048, rank=160, chunk_size=8, random_init=True, seed=1234,
                  num_layers=None, chunk_layout="reference", v_offload=True, overlap_attention=False, max_new_tokens=1024,
                  resident_sets=None, minference=False, minference_pattern=None, weight_dtype="bf16", fp8_rows="fallback",
-                 v_dtype="bf16", mxfp4_rows="fallback"):
+                 v_dtype="bf16", mxfp4_rows="fallback", landmark_dtype="bf16"):
         if weight_dtype not in WEIGHT_DTYPES:       # (before anything is allocated)
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
         if v_dtype not in tensor_op.V_DTYPES:
             raise ValueError(f"v_dtype must be one of {tensor_op.V_DTYPES}, got {v_dtype!r}")
         # "fp8_e4m3": the ShadowKV cache keeps its chunked V table as e4m3 bytes; attn_mode="full" has no table
         self.v_dtype = v_dtype
+        if landmark_dtype not in tensor_op.LANDMARK_DTYPES:
+            raise ValueError(f"landmark_dtype must be one of {tensor_op.LANDMARK_DTYPES}, got {landmark_dtype!r}")
+        # "fp8_e4m3": the ShadowKV cache keeps its landmark table as e4m3 bytes; attn_mode="full" has no landmarks
+        self.landmark_dtype = landmark_dtype
         if fp8_rows not in tensor_op.FP8_ROWS_MODES:
             raise ValueError(f"fp8_rows must be one of {tensor_op.FP8_ROWS_MODES}, got {fp8_rows!r}")
         # FP8 weights with 2..32 sequences: "native" = skv_linear_rows_fp8, "fallback" = dequantise + F.linear (DESIGN.md section
@@ -204,7 +208,8 @@ class DecoderLM:
         else:
             self.kv_cache = ShadowKVCache_CPU(_CacheCfg, batch_size=batch_size, max_length=max_length, device=device,
                                               dtype=dtype, sparse_budget=sparse_budget, chunk_size=chunk_size,
-                                              rank=rank, v_offload=v_offload, resident_sets=resident_sets, v_dtype=v_dtype)
+                                              rank=rank, v_offload=v_offload, resident_sets=resident_sets, v_dtype=v_dtype,
+                                              landmark_dtype=landmark_dtype)
         self.query_hook = None   # optional: q -> q used for selection/attention (bench: synthetic query walk)
         self._sampler_state = {}
         # lm_head -> sampler through range maxima (round 4): the lm_head launch of forward_fused leaves the largest of every 16

@@ -66,6 +66,7 @@ def dequantize_fp8_rows(w8, scale, dtype=torch.bfloat16):
 
 # ---------------------------------------------------------------------------- FP8 V offload table
 V_DTYPES = ("bf16", "fp8_e4m3")
+LANDMARK_DTYPES = ("bf16", "fp8_e4m3")             # the landmark table of the decode scan: same rule, per landmark row
 V_SCALE_MIN_EXP, V_SCALE_MAX_EXP = -100, 100
 
 

@@ -11,7 +11,11 @@ graph at bs > 1 is not part of the FP8 rows work) as a triple over one context, 
 FP8 model with the dequantising fallback, the FP8 model with fp8_rows="native" (skv_linear_rows_fp8).
 --weight-dtype mxfp4 --batch B: the same triple for MXFP4 weights - bf16, the MXFP4 model with the dequantising fallback, the
 MXFP4 model with mxfp4_rows="native" (skv_linear_rows_mxfp4); --mxfp4-rows {both,fallback,native} picks
-which of the two MXFP4 measurements run (the fallback dequantises every matrix on every step: it is the slow one)."""
+which of the two MXFP4 measurements run (the fallback dequantises every matrix on every step: it is the slow one).
+--landmark-dtype fp8_e4m3 (any --batch): bf16 weights throughout, ONE model and context; the cache's landmark
+table is swapped between the bf16 means and their FP8 quantisation (table + row scales) and the two are timed alternately,
+--repeats times each (bs 1: captured graph with early fetch + near staging; bs > 1: eager decode_step), then a short probe run
+per dtype over the same query walk reports how many of the selected chunks the two share per step."""
 import argparse
 import os
 import sys
@@ -105,6 +109,70 @@ def batched(a, wd="fp8_e4m3"):
     return lines
 
 
+def selected_sets(model, ctx, steps, seed=99):
+    """bool [steps, L, bs, kv, n_chunks]: the chunks in the resident set after each eager step of a fixed query walk (with
+    resident_sets == select_sets that IS the step's selection; it depends on the walk and the landmarks only)"""
+    c = model.kv_cache
+    c.kv_offset, c.gen_offset = ctx, 0
+    walk = llama.QueryWalk(model, step=0.3, seed=seed)
+    tok = torch.full((model.batch_size, 1), 17, device=model.device)
+    out = []
+    for _ in range(steps):
+        walk.advance()
+        tok = model.decode_step(tok, temperature=0.0, q_table=walk.qb)
+        ids = c.position_ids.clamp_min(0)
+        out.append(torch.zeros(*ids.shape[:-1], c.v_cache_cpu.shape[-2], dtype=torch.bool, device=ids.device).scatter_(-1, ids, True))
+    torch.cuda.synchronize()
+    return torch.stack(out)
+
+
+def landmark_ab(a):
+    from shadowkv_amd import tensor_op
+    ctx, dev, bs = 122 * 1024, "cuda:0", a.batch
+    model = llama.DecoderLM(cfg=llama.LLAMA_3_1_8B, batch_size=bs, max_length=ctx, device=dev, sparse_budget=2048, rank=160,
+                            chunk_size=8, num_layers=a.layers, chunk_layout="inplace", overlap_attention=True,
+                            max_new_tokens=max(1024, 8 * (a.warmup + a.steps) + 256))
+    llama.build_synthetic_context(model, ctx, seed=4321)
+    c = model.kv_cache
+    if bs == 1:
+        c.enable_early_fetch(near=True)
+    lm = c.k_landmark
+    table = torch.zeros(lm.shape, dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
+    scale = torch.ones(lm.shape[:-1], dtype=torch.float32, device=dev)
+    for l in range(lm.shape[0]):
+        tensor_op.quantize_v_rows(lm[l], table[l].view(bs, lm.shape[2], -1), scale[l])
+    torch.cuda.synchronize()
+    forms = {"bf16": (lm, None), a.landmark_dtype: (table, scale)}
+
+    def use(dt):
+        c.k_landmark, c.k_landmark_scale = forms[dt]
+        c.landmark_dtype = dt
+
+    tps = {dt: [] for dt in forms}
+    for _ in range(a.repeats):
+        for dt in forms:
+            use(dt)
+            tps[dt].append(run(model, ctx, a.steps, a.warmup) if bs == 1 else run_eager(model, ctx, a.steps, a.warmup))
+    sets = {}
+    for dt in forms:
+        use(dt)
+        sets[dt] = selected_sets(model, ctx, 8)
+    S = c.select_sets
+    both = (sets["bf16"] & sets[a.landmark_dtype]).sum(-1).float() / S                 # [steps, L, bs, kv]
+    lines = [f"# tools/fp8_e2e.py --landmark-dtype {a.landmark_dtype} --batch {bs} on {torch.cuda.get_device_name(0)}: 122 K synthetic context, "
+             f"budget 2048, in-place + overlap_attention, {'hipGraph, early fetch + near staging' if bs == 1 else 'eager decode_step'}, "
+             f"{model.num_layers} layers, {a.steps} steps after {a.warmup} warm-up steps, {a.repeats} alternating repeats"]
+    for dt, v in tps.items():
+        v = sorted(v)
+        lines.append(f"bs {bs:2d} landmark_dtype {dt:<9} {v[len(v) // 2]:8.2f} tokens/s (median; all: {' '.join(f'{x:.2f}' for x in v)})  "
+                     f"landmark table {forms[dt][0][0].numel() * forms[dt][0].element_size() / 1e6:7.1f} MB per layer")
+    med = {dt: sorted(v)[len(v) // 2] for dt, v in tps.items()}
+    lines.append(f"bs {bs:2d} fp8 : bf16 landmarks tokens/s ratio {med[a.landmark_dtype] / med['bf16']:.3f}")
+    lines.append(f"bs {bs:2d} selected chunks shared by the two, per step (mean over layers and heads): "
+                 + " ".join(f"{100 * float(x):.1f}%" for x in both.mean(dim=(1, 2, 3))) + f"   min over (step, layer, head) {100 * float(both.min()):.1f}%")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=64)
@@ -114,7 +182,17 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--weight-dtype", dest="weight_dtype", choices=("fp8_e4m3", "mxfp4"), default=None)
     ap.add_argument("--mxfp4-rows", dest="mxfp4_rows", choices=("both", "fallback", "native"), default="both")
+    ap.add_argument("--landmark-dtype", dest="landmark_dtype", choices=("fp8_e4m3",), default=None)
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
+    if a.landmark_dtype:
+        lines = landmark_ab(a)
+        print("\n".join(lines))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     wd = a.weight_dtype or "fp8_e4m3"
     if a.batch > 1:
         lines = batched(a, wd)
