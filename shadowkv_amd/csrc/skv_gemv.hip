@@ -228,17 +228,15 @@ __global__ __launch_bounds__(256, R <= 2 ? 4 : 3) void skv_gemv_kernel(const bf1
     skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias != nullptr, eop, y, qe, range_max);
 }
 
-// the bf16 launch of skv_gemv_dispatch
-struct GemvBf16 {
+// the bf16 format of the host entries (skv_gemv_frame.h)
+struct GemvBf16 : GemvArgs {
+    static constexpr int K_STEP = 8, K_MIN = 512;
+    static constexpr bool SCALED = false;
     static constexpr bool Q_ROWS_ALONE = true;       // N = Hq * 128: skv_q_gemv_rope
-    const bf16_t *W, *x, *bias;
-    bf16_t* y;
-    int N, K;
-    const bf16_t *residual, *w_norm;
-    bf16_t* h_out;
-    float eps;
-    QkvEpilogue qe;
-    hipStream_t st;
+    static constexpr bool NEAR_ROLE_ARGS_FIRST = true;      // a near-pull entry checks the role's arguments first, then the GEMV's own
+    static constexpr bool QKV_REFUSES_NO_HEADS = false;     // the QKV entry with no heads: left to the GEMV's checks of N and K
+    const bf16_t* W;
+    GemvBf16(const GemvArgs& a, const void* w, const void*) : GemvArgs(a), W((const bf16_t*)w) {}
     template <int R, bool SILU, bool NORM, bool QKV, bool RMAX, bool NEARP>
     void launch(int grid, int I, uint16_t* range_max, const NearPull& near) const {
         hipLaunchKernelGGL((skv_gemv_kernel<R, SILU, NORM, QKV, RMAX, NEARP>), dim3(grid), dim3(256), 0, st, W, x, bias, y, N, K, I,
@@ -246,56 +244,37 @@ struct GemvBf16 {
     }
 };
 
-static int launch_gemv(const void* W, const void* x, const void* bias, void* y, int N, int K, int fuse_silu_mul,
-                       const void* residual, const void* w_norm, void* h_out, float eps, bool norm, hipStream_t st,
-                       const QkvEpilogue* qkv = nullptr, uint16_t* range_max = nullptr, const NearPull* near = nullptr) {
-    if (!W || !x || (!y && !qkv) || N < 1) return SKV_ERR_ARG;
-    if (K % 8 || K < 512) return SKV_ERR_UNSUPPORTED;
-    if (norm && (K != 4096 || !w_norm)) return SKV_ERR_UNSUPPORTED;
-    const GemvBf16 l{(const bf16_t*)W, (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, (const bf16_t*)residual,
-                     (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qkv ? *qkv : QkvEpilogue{}, st};
-    return skv_gemv_dispatch(l, N, bias != nullptr, fuse_silu_mul != 0, norm, qkv, range_max, near);
-}
-
 extern "C" int skv_gemv_bf16(const void* W, const void* x, const void* bias, void* y, int N, int K, int fuse_silu_mul,
                              skv_stream_t stream) {
-    return launch_gemv(W, x, bias, y, N, K, fuse_silu_mul, nullptr, nullptr, nullptr, 0.f, false, (hipStream_t)stream);
+    return skv_gemv_entry<GemvBf16>(W, nullptr, x, bias, y, N, K, fuse_silu_mul, stream);
 }
 
 extern "C" int skv_norm_gemv_bf16(const void* W, const void* x, const void* residual, const void* norm_weight, float eps,
                                   void* h_out, const void* bias, void* y, int N, int K, int fuse_silu_mul,
                                   skv_stream_t stream) {
-    return launch_gemv(W, x, bias, y, N, K, fuse_silu_mul, residual, norm_weight, h_out, eps, true, (hipStream_t)stream);
+    return skv_norm_gemv_entry<GemvBf16>(W, nullptr, x, residual, norm_weight, eps, h_out, bias, y, N, K, fuse_silu_mul, stream);
 }
 
 extern "C" int skv_norm_gemv_near_pull_bf16(const void* W, const void* x, const void* residual, const void* norm_weight, float eps,
                                             void* h_out, void* y, int N, int K, void* early_state, int blocks, int groups,
                                             int n_landmarks, int n_chunks, int early_max, const void* v_host,
                                             long long host_block_stride, int pull_parts, int active_lists, skv_stream_t stream) {
-    NearPull np{};
-    const int rc = near_pull_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, 0,
-                                active_lists);
-    if (rc != SKV_OK) return rc;
-    return launch_gemv(W, x, nullptr, y, N, K, 1, residual, norm_weight, h_out, eps, true, (hipStream_t)stream, nullptr, nullptr, &np);
+    return skv_norm_gemv_near_pull_entry<GemvBf16>(W, nullptr, x, residual, norm_weight, eps, h_out, y, N, K, early_state, blocks, groups,
+                                                   n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, active_lists,
+                                                   stream);
 }
 
-// the down projection (skv_gemv_bf16, N <= 8192) with the pull role of near-miss list `list` (1: ranks S + 65 .. S + 128)
 extern "C" int skv_gemv_near_pull_bf16(const void* W, const void* x, const void* bias, void* y, int N, int K, void* early_state,
                                        int blocks, int groups, int n_landmarks, int n_chunks, int early_max, const void* v_host,
                                        long long host_block_stride, int pull_parts, int list, skv_stream_t stream) {
-    NearPull np{};
-    const int rc = near_pull_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, list,
-                                SKV_NEAR_LISTS);
-    if (rc != SKV_OK) return rc;
-    return launch_gemv(W, x, bias, y, N, K, 0, nullptr, nullptr, nullptr, 0.f, false, (hipStream_t)stream, nullptr, nullptr, &np);
+    return skv_gemv_near_pull_entry<GemvBf16>(W, nullptr, x, bias, y, N, K, early_state, blocks, groups, n_landmarks, n_chunks, early_max,
+                                              v_host, host_block_stride, pull_parts, list, stream);
 }
 
 extern "C" int skv_norm_gemv_rangemax_bf16(const void* W, const void* x, const void* residual, const void* norm_weight, float eps,
                                            void* h_out, const void* bias, void* y, int N, int K, void* range_max,
                                            skv_stream_t stream) {
-    if (!range_max) return SKV_ERR_ARG;
-    return launch_gemv(W, x, bias, y, N, K, 0, residual, norm_weight, h_out, eps, true, (hipStream_t)stream, nullptr,
-                       (uint16_t*)range_max);
+    return skv_norm_gemv_rangemax_entry<GemvBf16>(W, nullptr, x, residual, norm_weight, eps, h_out, bias, y, N, K, range_max, stream);
 }
 
 extern "C" int skv_qkv_gemv_rope_update(const void* Wqkv, const void* x, const void* residual, const void* norm_weight,
@@ -304,12 +283,9 @@ extern "C" int skv_qkv_gemv_rope_update(const void* Wqkv, const void* x, const v
                                         void* v_cache, int K, int q_heads, int kv_heads, int head_dim,
                                         long long cos_sin_stride, int cos_sin_rows, long long cache_stride_h, int cache_rows,
                                         int rope_mode, skv_stream_t stream) {
-    if (!cos_sin || !pos || !row_idx || !q_out || !k_cache || !v_cache || cos_sin_rows < 1) return SKV_ERR_ARG;
-    if (head_dim != 128 || (rope_mode != 1 && rope_mode != 2)) return SKV_ERR_UNSUPPORTED;
-    QkvEpilogue qe{(const bf16_t*)cos_sin, pos, row_idx, (const bf16_t*)q_override, (bf16_t*)q_out, (bf16_t*)k_cache,
-                   (bf16_t*)v_cache, cos_sin_stride, cache_stride_h, q_heads, kv_heads, cache_rows, rope_mode == 2, cos_sin_rows};
-    return launch_gemv(Wqkv, x, bias, nullptr, (q_heads + 2 * kv_heads) * 128, K, 0, residual, norm_weight, h_out, eps,
-                       norm_weight != nullptr, (hipStream_t)stream, &qe);
+    return skv_qkv_gemv_rope_update_entry<GemvBf16>(Wqkv, nullptr, x, residual, norm_weight, eps, h_out, bias, cos_sin, pos, row_idx,
+                                                    q_override, q_out, k_cache, v_cache, K, q_heads, kv_heads, head_dim, cos_sin_stride,
+                                                    cos_sin_rows, cache_stride_h, cache_rows, rope_mode, stream);
 }
 
 // The q rows of skv_qkv_gemv_rope_update alone: same kernel, same waves, a grid that ends behind the last q head.  The k / v
@@ -323,5 +299,5 @@ extern "C" int skv_q_gemv_rope(const void* Wqkv, const void* x, const void* resi
     // (no wave of this grid owns a k or v head: the caches are never touched, and the row index every wave's lane 0 loads goes unused)
     QkvEpilogue qe{(const bf16_t*)cos_sin, pos, pos, (const bf16_t*)q_override, (bf16_t*)q_out, nullptr, nullptr, cos_sin_stride, 0,
                    q_heads, kv_heads, 0, rope_mode == 2, cos_sin_rows};
-    return launch_gemv(Wqkv, x, bias, nullptr, q_heads * 128, K, 0, residual, norm_weight, h_out, eps, true, (hipStream_t)stream, &qe);
+    return skv_gemv_launch<GemvBf16>(Wqkv, nullptr, x, bias, nullptr, q_heads * 128, K, 0, residual, norm_weight, h_out, eps, true, stream, &qe);
 }

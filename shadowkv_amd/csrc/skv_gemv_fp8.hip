@@ -140,103 +140,58 @@ __global__ __launch_bounds__(256) void skv_gemv_fp8_kernel(const uint8_t* __rest
     skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias, y, qe, range_max, x);
 }
 
-// every check of the GEMV's own arguments; host only, before any HIP call
-static int gemv_fp8_args(const void* W, const void* scale, const void* x, const void* y, bool qkv, int N, int K, bool norm,
-                         const void* w_norm) {
-    if (!W || !scale || !x || (!y && !qkv) || N < 1) return SKV_ERR_ARG;
-    if (K % 16 || K < 1024) return SKV_ERR_UNSUPPORTED;
-    if (norm && (K != 4096 || !w_norm)) return SKV_ERR_UNSUPPORTED;
-    return SKV_OK;
-}
-
-// the FP8 launch of skv_gemv_dispatch
-struct GemvFp8 {
+// the FP8 format of the host entries (skv_gemv_frame.h)
+struct GemvFp8 : GemvArgs {
+    static constexpr int K_STEP = 16, K_MIN = 1024;
+    static constexpr bool SCALED = true;
     static constexpr bool Q_ROWS_ALONE = false;
+    static constexpr bool NEAR_ROLE_ARGS_FIRST = false;      // a near-pull entry checks the GEMV's own arguments first, then the role's
+    static constexpr bool QKV_REFUSES_NO_HEADS = true;     // the QKV entry with no heads: SKV_ERR_ARG from the entry itself
     const uint8_t* W;
     const float* scale;
-    const bf16_t *x, *bias;
-    bf16_t* y;
-    int N, K;
-    const bf16_t *residual, *w_norm;
-    bf16_t* h_out;
-    float eps;
-    QkvEpilogue qe;
-    hipStream_t st;
+    GemvFp8(const GemvArgs& a, const void* w, const void* s) : GemvArgs(a), W((const uint8_t*)w), scale((const float*)s) {}
     template <int R, bool SILU, bool NORM, bool QKV, bool RMAX, bool NEARP>
     void launch(int grid, int I, uint16_t* range_max, const NearPull& near) const {
-        hipLaunchKernelGGL((skv_gemv_fp8_kernel<R, SILU, NORM, QKV, RMAX, NEARP>), dim3(grid), dim3(256), 0, st, W, scale, x, bias, y, N,
-                           K, I, residual, w_norm, h_out, eps, qe, range_max, near);
+        hipLaunchKernelGGL((skv_gemv_fp8_kernel<R, SILU, NORM, QKV, RMAX, NEARP>), dim3(grid), dim3(256), 0, st, W, scale, x, bias, y, N, K, I,
+                           residual, w_norm, h_out, eps, qe, range_max, near);
     }
 };
 
-static int launch_gemv_fp8(const void* W, const void* scale, const void* x, const void* bias, void* y, int N, int K,
-                           int fuse_silu_mul, const void* residual, const void* w_norm, void* h_out, float eps, bool norm,
-                           hipStream_t st, const QkvEpilogue* qkv = nullptr, uint16_t* range_max = nullptr,
-                           const NearPull* near = nullptr) {
-    const int rc = gemv_fp8_args(W, scale, x, y, qkv != nullptr, N, K, norm, w_norm);
-    if (rc != SKV_OK) return rc;
-    const GemvFp8 l{(const uint8_t*)W, (const float*)scale, (const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K,
-                    (const bf16_t*)residual, (const bf16_t*)w_norm, (bf16_t*)h_out, eps, qkv ? *qkv : QkvEpilogue{}, st};
-    return skv_gemv_dispatch(l, N, bias != nullptr, fuse_silu_mul != 0, norm, qkv, range_max, near);
-}
-
 extern "C" int skv_gemv_fp8(const void* W8, const void* scale, const void* x, const void* bias, void* y, int N, int K,
-                            int fuse_silu_mul, skv_stream_t stream) {
-    return launch_gemv_fp8(W8, scale, x, bias, y, N, K, fuse_silu_mul, nullptr, nullptr, nullptr, 0.f, false, (hipStream_t)stream);
+        int fuse_silu_mul, skv_stream_t stream) {
+    return skv_gemv_entry<GemvFp8>(W8, scale, x, bias, y, N, K, fuse_silu_mul, stream);
 }
 
 extern "C" int skv_norm_gemv_fp8(const void* W8, const void* scale, const void* x, const void* residual, const void* norm_weight,
-                                 float eps, void* h_out, const void* bias, void* y, int N, int K, int fuse_silu_mul,
-                                 skv_stream_t stream) {
-    return launch_gemv_fp8(W8, scale, x, bias, y, N, K, fuse_silu_mul, residual, norm_weight, h_out, eps, true, (hipStream_t)stream);
+        float eps, void* h_out, const void* bias, void* y, int N, int K, int fuse_silu_mul, skv_stream_t stream) {
+    return skv_norm_gemv_entry<GemvFp8>(W8, scale, x, residual, norm_weight, eps, h_out, bias, y, N, K, fuse_silu_mul, stream);
 }
 
 extern "C" int skv_norm_gemv_rangemax_fp8(const void* W8, const void* scale, const void* x, const void* residual,
-                                          const void* norm_weight, float eps, void* h_out, const void* bias, void* y, int N, int K,
-                                          void* range_max, skv_stream_t stream) {
-    if (!range_max) return SKV_ERR_ARG;
-    return launch_gemv_fp8(W8, scale, x, bias, y, N, K, 0, residual, norm_weight, h_out, eps, true, (hipStream_t)stream, nullptr,
-                           (uint16_t*)range_max);
+        const void* norm_weight, float eps, void* h_out, const void* bias, void* y, int N, int K, void* range_max, skv_stream_t stream) {
+    return skv_norm_gemv_rangemax_entry<GemvFp8>(W8, scale, x, residual, norm_weight, eps, h_out, bias, y, N, K, range_max, stream);
 }
 
 extern "C" int skv_qkv_gemv_rope_update_fp8(const void* Wqkv8, const void* scale, const void* x, const void* residual,
-                                            const void* norm_weight, float eps, void* h_out, const void* bias, const void* cos_sin,
-                                            const int64_t* pos, const int64_t* row_idx, const void* q_override, void* q_out,
-                                            void* k_cache, void* v_cache, int K, int q_heads, int kv_heads, int head_dim,
-                                            long long cos_sin_stride, int cos_sin_rows, long long cache_stride_h, int cache_rows,
-                                            int rope_mode, skv_stream_t stream) {
-    if (!cos_sin || !pos || !row_idx || !q_out || !k_cache || !v_cache || cos_sin_rows < 1 || q_heads < 1 || kv_heads < 1)
-        return SKV_ERR_ARG;
-    if (head_dim != 128 || (rope_mode != 1 && rope_mode != 2)) return SKV_ERR_UNSUPPORTED;
-    QkvEpilogue qe{(const bf16_t*)cos_sin, pos, row_idx, (const bf16_t*)q_override, (bf16_t*)q_out, (bf16_t*)k_cache,
-                   (bf16_t*)v_cache, cos_sin_stride, cache_stride_h, q_heads, kv_heads, cache_rows, rope_mode == 2, cos_sin_rows};
-    return launch_gemv_fp8(Wqkv8, scale, x, bias, nullptr, (q_heads + 2 * kv_heads) * 128, K, 0, residual, norm_weight, h_out, eps,
-                           norm_weight != nullptr, (hipStream_t)stream, &qe);
+        const void* norm_weight, float eps, void* h_out, const void* bias, const void* cos_sin, const int64_t* pos, const int64_t* row_idx,
+        const void* q_override, void* q_out, void* k_cache, void* v_cache, int K, int q_heads, int kv_heads, int head_dim,
+        long long cos_sin_stride, int cos_sin_rows, long long cache_stride_h, int cache_rows, int rope_mode, skv_stream_t stream) {
+    return skv_qkv_gemv_rope_update_entry<GemvFp8>(Wqkv8, scale, x, residual, norm_weight, eps, h_out, bias, cos_sin, pos, row_idx,
+                                                    q_override, q_out, k_cache, v_cache, K, q_heads, kv_heads, head_dim, cos_sin_stride,
+                                                    cos_sin_rows, cache_stride_h, cache_rows, rope_mode, stream);
 }
 
 extern "C" int skv_norm_gemv_near_pull_fp8(const void* W8, const void* scale, const void* x, const void* residual,
-                                           const void* norm_weight, float eps, void* h_out, void* y, int N, int K, void* early_state,
-                                           int blocks, int groups, int n_landmarks, int n_chunks, int early_max, const void* v_host,
-                                           long long host_block_stride, int pull_parts, int active_lists, skv_stream_t stream) {
-    int rc = gemv_fp8_args(W8, scale, x, y, false, N, K, true, norm_weight);
-    if (rc != SKV_OK) return rc;
-    NearPull np{};
-    rc = near_pull_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, 0,
-                      active_lists);
-    if (rc != SKV_OK) return rc;
-    return launch_gemv_fp8(W8, scale, x, nullptr, y, N, K, 1, residual, norm_weight, h_out, eps, true, (hipStream_t)stream, nullptr,
-                           nullptr, &np);
+        const void* norm_weight, float eps, void* h_out, void* y, int N, int K, void* early_state, int blocks, int groups, int n_landmarks,
+        int n_chunks, int early_max, const void* v_host, long long host_block_stride, int pull_parts, int active_lists, skv_stream_t stream) {
+    return skv_norm_gemv_near_pull_entry<GemvFp8>(W8, scale, x, residual, norm_weight, eps, h_out, y, N, K, early_state, blocks, groups,
+                                                   n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, active_lists,
+                                                   stream);
 }
 
 extern "C" int skv_gemv_near_pull_fp8(const void* W8, const void* scale, const void* x, const void* bias, void* y, int N, int K,
-                                      void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
-                                      const void* v_host, long long host_block_stride, int pull_parts, int list, skv_stream_t stream) {
-    int rc = gemv_fp8_args(W8, scale, x, y, false, N, K, false, nullptr);
-    if (rc != SKV_OK) return rc;
-    NearPull np{};
-    rc = near_pull_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, list,
-                      SKV_NEAR_LISTS);
-    if (rc != SKV_OK) return rc;
-    return launch_gemv_fp8(W8, scale, x, bias, y, N, K, 0, nullptr, nullptr, nullptr, 0.f, false, (hipStream_t)stream, nullptr, nullptr,
-                           &np);
+        void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max, const void* v_host,
+        long long host_block_stride, int pull_parts, int list, skv_stream_t stream) {
+    return skv_gemv_near_pull_entry<GemvFp8>(W8, scale, x, bias, y, N, K, early_state, blocks, groups, n_landmarks, n_chunks, early_max,
+                                              v_host, host_block_stride, pull_parts, list, stream);
 }

@@ -1,10 +1,11 @@
-// The frame the decode GEMV kernels share: skv_gemv_kernel (skv_gemv.hip, bf16 weights) and skv_gemv_fp8_kernel
-// (skv_gemv_fp8.hip, e4m3 weights + a row scale) differ only in how they stream and multiply a weight row.  Everything
-// around that stream is stated here once: the near-pull role in front of the grid, which rows a wave owns, a row's
-// reduction, the epilogue, and on the host the branch tree that picks a kernel instance.  The residual add + RMSNorm
-// prologue both kernels call is skv_norm_prologue_4096 (skv_kvproj.h), near_pull_of is next to skv_near_pull (skv_launch.h).
+// The frame the decode GEMV kernels share: skv_gemv_kernel (skv_gemv.hip, bf16 weights), skv_gemv_fp8_kernel (skv_gemv_fp8.hip,
+// e4m3 weights + a row scale) and skv_gemv_mxfp4_kernel (skv_gemv_mxfp4.hip, e2m1 nibbles + e8m0 block scales) differ only in how
+// they stream and multiply a weight row.  Everything around that stream is stated here once: the near-pull role in front of the
+// grid, which rows a wave owns, a row's reduction, the epilogue, and on the host the branch tree that picks a kernel instance and
+// the bodies of the extern "C" entries.  The residual add + RMSNorm prologue the kernels call is skv_norm_prologue_4096
+// (skv_kvproj.h), near_pull_of is next to skv_near_pull (skv_launch.h).
 //
-// Template parameters of both kernels: R rows per wave; SILU_PAIR: W = [gate; up], the wave's rows are R / 2 (gate, up)
+// Template parameters of the kernels: R rows per wave; SILU_PAIR: W = [gate; up], the wave's rows are R / 2 (gate, up)
 // pairs and y[i] = bf16(silu(gate_i)) * up_i; NORM: x is the pre-norm hidden state (K == 4096); QKV: W = fused [q; k; v] of
 // ONE token (head_dim 128), the wave's rows are R / 2 rotation pairs of one head - NeoX (t, t+64), GLM (2t, 2t+1) - and lane
 // 0 rotates and writes q / the cache row (skv_qkv_epilogue); RMAX (lm_head, N % 16 == 0): the workgroup also leaves the
@@ -135,9 +136,30 @@ __device__ __forceinline__ void skv_gemv_epilogue(const int (&rows)[R], const fl
     skv_gemv_epilogue<R, SILU_PAIR, QKV, RMAX>(rows, tot, unit0, bx, tid, N, I, bias != nullptr, op, y, qe, range_max);
 }
 
-// Host: the kernel instance and the grid of a launch, for both formats.  L is the format's launcher: it holds the launch's
-// arguments, launch<R, SILU, NORM, QKV, RMAX, NEARP>(grid, I, range_max, near) starts its kernel, and L::Q_ROWS_ALONE says
-// whether the format has the q-only launch (N = Hq * 128).  The format checks its own arguments (pointers, K) before this.
+// Host.  A format is a struct L: GemvArgs (the arguments every format's kernel takes) plus its weight pointer - the scaled
+// formats: and the scale pointer behind it - built by L(args, W, scale), and
+//   K_STEP, K_MIN         K must be a multiple of the one and at least the other
+//   SCALED                a scale pointer follows W in every entry (bf16: absent - its forwarders pass nullptr, nothing reads it)
+//   Q_ROWS_ALONE          the format has the q-only launch (N = Hq * 128)
+//   launch<R, SILU, NORM, QKV, RMAX, NEARP>(grid, I, range_max, near)    starts the format's kernel
+// and the two places where the answers of bf16 and of the scaled formats to a refused call differ (tests/test_gemv_refusals_cpu.py
+// holds every entry to them):
+//   NEAR_ROLE_ARGS_FIRST  a near-pull entry checks the role's arguments (near_pull_of) before the GEMV's own: a call that is wrong
+//                         in both gets the role's code from bf16 and the GEMV's from FP8 / MXFP4
+//   QKV_REFUSES_NO_HEADS  the QKV entry refuses q_heads < 1 || kv_heads < 1 itself (SKV_ERR_ARG); bf16 has no such check there and
+//                         answers with whatever the GEMV's checks say about N = (q_heads + 2 * kv_heads) * 128 and K
+struct GemvArgs {
+    const bf16_t *x, *bias;
+    bf16_t* y;
+    int N, K;
+    const bf16_t *residual, *w_norm;
+    bf16_t* h_out;
+    float eps;
+    QkvEpilogue qe;
+    hipStream_t st;
+};
+
+// the kernel instance and the grid of a launch, for every format
 template <class L>
 static int skv_gemv_dispatch(const L& l, int N, bool bias, bool fuse_silu_mul, bool norm, const QkvEpilogue* qkv, uint16_t* range_max,
                              const NearPull* near) {
@@ -169,4 +191,93 @@ static int skv_gemv_dispatch(const L& l, int N, bool bias, bool fuse_silu_mul, b
     } else if (norm) l.template launch<4, false, true, false, false, false>((N + 15) / 16, 0, nullptr, none);
     else l.template launch<4, false, false, false, false, false>((N + 15) / 16, 0, nullptr, none);
     return hipGetLastError() == hipSuccess ? SKV_OK : SKV_ERR_LAUNCH;
+}
+
+// every check of the GEMV's own arguments; host only, before any HIP call
+template <class L>
+static int skv_gemv_check(const void* W, const void* scale, const void* x, const void* y, bool qkv, int N, int K, bool norm,
+                          const void* w_norm) {
+    if (!W || (L::SCALED && !scale) || !x || (!y && !qkv) || N < 1) return SKV_ERR_ARG;
+    if (K % L::K_STEP || K < L::K_MIN) return SKV_ERR_UNSUPPORTED;
+    if (norm && (K != 4096 || !w_norm)) return SKV_ERR_UNSUPPORTED;
+    return SKV_OK;
+}
+
+// check, build the format's launcher, dispatch
+template <class L>
+static int skv_gemv_launch(const void* W, const void* scale, const void* x, const void* bias, void* y, int N, int K, int fuse_silu_mul,
+                           const void* residual, const void* w_norm, void* h_out, float eps, bool norm, skv_stream_t stream,
+                           const QkvEpilogue* qkv = nullptr, uint16_t* range_max = nullptr, const NearPull* near = nullptr) {
+    const int rc = skv_gemv_check<L>(W, scale, x, y, qkv != nullptr, N, K, norm, w_norm);
+    if (rc != SKV_OK) return rc;
+    const L l(GemvArgs{(const bf16_t*)x, (const bf16_t*)bias, (bf16_t*)y, N, K, (const bf16_t*)residual, (const bf16_t*)w_norm,
+                       (bf16_t*)h_out, eps, qkv ? *qkv : QkvEpilogue{}, (hipStream_t)stream},
+              W, scale);
+    return skv_gemv_dispatch(l, N, bias != nullptr, fuse_silu_mul != 0, norm, qkv, range_max, near);
+}
+
+// The six kinds of entry; a format's extern "C" names forward to them.
+template <class L>
+static int skv_gemv_entry(const void* W, const void* scale, const void* x, const void* bias, void* y, int N, int K, int fuse_silu_mul,
+                          skv_stream_t stream) {
+    return skv_gemv_launch<L>(W, scale, x, bias, y, N, K, fuse_silu_mul, nullptr, nullptr, nullptr, 0.f, false, stream);
+}
+
+template <class L>
+static int skv_norm_gemv_entry(const void* W, const void* scale, const void* x, const void* residual, const void* norm_weight, float eps,
+                               void* h_out, const void* bias, void* y, int N, int K, int fuse_silu_mul, skv_stream_t stream) {
+    return skv_gemv_launch<L>(W, scale, x, bias, y, N, K, fuse_silu_mul, residual, norm_weight, h_out, eps, true, stream);
+}
+
+template <class L>
+static int skv_norm_gemv_rangemax_entry(const void* W, const void* scale, const void* x, const void* residual, const void* norm_weight,
+                                        float eps, void* h_out, const void* bias, void* y, int N, int K, void* range_max,
+                                        skv_stream_t stream) {
+    if (!range_max) return SKV_ERR_ARG;
+    return skv_gemv_launch<L>(W, scale, x, bias, y, N, K, 0, residual, norm_weight, h_out, eps, true, stream, nullptr, (uint16_t*)range_max);
+}
+
+template <class L>
+static int skv_qkv_gemv_rope_update_entry(const void* Wqkv, const void* scale, const void* x, const void* residual,
+                                          const void* norm_weight, float eps, void* h_out, const void* bias, const void* cos_sin,
+                                          const int64_t* pos, const int64_t* row_idx, const void* q_override, void* q_out, void* k_cache,
+                                          void* v_cache, int K, int q_heads, int kv_heads, int head_dim, long long cos_sin_stride,
+                                          int cos_sin_rows, long long cache_stride_h, int cache_rows, int rope_mode, skv_stream_t stream) {
+    if (!cos_sin || !pos || !row_idx || !q_out || !k_cache || !v_cache || cos_sin_rows < 1 ||
+        (L::QKV_REFUSES_NO_HEADS && (q_heads < 1 || kv_heads < 1)))
+        return SKV_ERR_ARG;
+    if (head_dim != 128 || (rope_mode != 1 && rope_mode != 2)) return SKV_ERR_UNSUPPORTED;
+    QkvEpilogue qe{(const bf16_t*)cos_sin, pos, row_idx, (const bf16_t*)q_override, (bf16_t*)q_out, (bf16_t*)k_cache,
+                   (bf16_t*)v_cache, cos_sin_stride, cache_stride_h, q_heads, kv_heads, cache_rows, rope_mode == 2, cos_sin_rows};
+    return skv_gemv_launch<L>(Wqkv, scale, x, bias, nullptr, (q_heads + 2 * kv_heads) * 128, K, 0, residual, norm_weight, h_out, eps,
+                              norm_weight != nullptr, stream, &qe);
+}
+
+// The near-miss pull role in front of the grid of the gate/up launch (norm, fused SiLU; list 0 of `active_lists`) ...
+template <class L>
+static int skv_norm_gemv_near_pull_entry(const void* W, const void* scale, const void* x, const void* residual, const void* norm_weight,
+                                         float eps, void* h_out, void* y, int N, int K, void* early_state, int blocks, int groups,
+                                         int n_landmarks, int n_chunks, int early_max, const void* v_host, long long host_block_stride,
+                                         int pull_parts, int active_lists, skv_stream_t stream) {
+    NearPull np{};
+    int rc = L::NEAR_ROLE_ARGS_FIRST ? SKV_OK : skv_gemv_check<L>(W, scale, x, y, false, N, K, true, norm_weight);
+    if (rc == SKV_OK)
+        rc = near_pull_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, 0,
+                          active_lists);
+    if (rc != SKV_OK) return rc;
+    return skv_gemv_launch<L>(W, scale, x, nullptr, y, N, K, 1, residual, norm_weight, h_out, eps, true, stream, nullptr, nullptr, &np);
+}
+
+// ... and of the down projection (N <= 8192), with near-miss list `list` (1: ranks S + 65 .. S + 128)
+template <class L>
+static int skv_gemv_near_pull_entry(const void* W, const void* scale, const void* x, const void* bias, void* y, int N, int K,
+                                    void* early_state, int blocks, int groups, int n_landmarks, int n_chunks, int early_max,
+                                    const void* v_host, long long host_block_stride, int pull_parts, int list, skv_stream_t stream) {
+    NearPull np{};
+    int rc = L::NEAR_ROLE_ARGS_FIRST ? SKV_OK : skv_gemv_check<L>(W, scale, x, y, false, N, K, false, nullptr);
+    if (rc == SKV_OK)
+        rc = near_pull_of(np, early_state, blocks, groups, n_landmarks, n_chunks, early_max, v_host, host_block_stride, pull_parts, list,
+                          SKV_NEAR_LISTS);
+    if (rc != SKV_OK) return rc;
+    return skv_gemv_launch<L>(W, scale, x, bias, y, N, K, 0, nullptr, nullptr, nullptr, 0.f, false, stream, nullptr, nullptr, &np);
 }

@@ -84,11 +84,8 @@ class DecoderLayer:
 
 
 def _dequantized(w, sc):
-    if sc is None:
-        return w
-    if w.dtype == torch.uint8:
-        return tensor_op.dequantize_mxfp4_rows(w, sc, torch.bfloat16)
-    return tensor_op.dequantize_fp8_rows(w, sc, torch.bfloat16)
+    fmt = tensor_op.weight_format(w, sc)
+    return w if fmt.dequantize is None else fmt.dequantize(w, sc, torch.bfloat16)
 
 
 def build_cos_sin_cache(cfg, max_pos, device, dtype):
@@ -148,6 +145,7 @@ class DecoderLM:
         self.landmark_dtype = landmark_dtype
         if fp8_rows not in tensor_op.FP8_ROWS_MODES:
             raise ValueError(f"fp8_rows must be one of {tensor_op.FP8_ROWS_MODES}, got {fp8_rows!r}")
+        self._rows_modes = {}       # the rows keywords every decode projection call is handed (**): self.fp8_rows, self.mxfp4_rows
         # FP8 weights with 2..32 sequences: "native" = skv_linear_rows_fp8, "fallback" = dequantise + F.linear (DESIGN.md section
         # 10.1); read only where a w_scale is passed, so it is inert on a bf16 model until quantize_weights()
         self.fp8_rows = fp8_rows
@@ -228,6 +226,11 @@ class DecoderLM:
         if weight_dtype != "bf16":      # random bf16 init, then quantised: the same seed gives the bf16 model's weights, quantised
             self.quantize_weights(dtype=weight_dtype)
 
+    # the two rows modes read and written as attributes; one dict holds them, so a call site passes both without building anything
+    fp8_rows = property(lambda self: self._rows_modes["fp8_rows"], lambda self, mode: self._rows_modes.__setitem__("fp8_rows", mode))
+    mxfp4_rows = property(lambda self: self._rows_modes["mxfp4_rows"],
+                          lambda self, mode: self._rows_modes.__setitem__("mxfp4_rows", mode))
+
     def quantize_weights(self, pow2_scale=False, dtype="fp8_e4m3"):
         """Weight-only quantisation in place: wqkv, wo, gate_up_proj, down_proj of every layer and the lm_head become
         "fp8_e4m3": float8_e4m3fn with one f32 scale per output row (`<name>_scale`, tensor_op.quantize_fp8_rows), or
@@ -243,7 +246,7 @@ class DecoderLM:
             raise ValueError(f"the model's weights are {self.weight_dtype} already: quantise a bf16 model to {dtype}")
 
         def quantize(w):
-            return tensor_op.quantize_mxfp4_rows(w) if dtype == "mxfp4" else tensor_op.quantize_fp8_rows(w, pow2_scale=pow2_scale)
+            return tensor_op.WEIGHT_FORMATS[dtype].quantize(w, pow2_scale=pow2_scale)
 
         for layer in self.layers:
             for name in DecoderLayer.MATRICES:
@@ -307,8 +310,7 @@ class DecoderLM:
             sc["i"] ^= 1                                        # (a new layer: the other buffer set)
             _, qkv = tensor_op.norm_linear_decode(hidden_states, None, layer.input_layernorm_weight,
                                                   layer.input_layernorm_variance_epsilon, layer.wqkv, layer.bqkv,
-                                                  out=sc["sets"][sc["i"]]["qkv"], w_scale=layer.wqkv_scale, fp8_rows=self.fp8_rows,
-                                                  mxfp4_rows=self.mxfp4_rows)
+                                                  out=sc["sets"][sc["i"]]["qkv"], w_scale=layer.wqkv_scale, **self._rows_modes)
         else:
             hs = tensor_op.layer_norm(hidden_states, layer.input_layernorm_variance_epsilon, layer.input_layernorm_weight)
             qkv = F.linear(hs, layer.prefill_weight("wqkv"), layer.bqkv)
@@ -374,8 +376,7 @@ class DecoderLM:
         if attn_output.shape[1] == 1 and attn_output.is_cuda:       # one decode token per sequence: native kernels
             sc = self._decode_scratch(attn_output.shape[0])
             cur = sc["sets"][sc["i"]]
-            o = tensor_op.linear_decode(attn_output, layer.wo, out=cur["o"], w_scale=layer.wo_scale, fp8_rows=self.fp8_rows,
-                                        mxfp4_rows=self.mxfp4_rows)
+            o = tensor_op.linear_decode(attn_output, layer.wo, out=cur["o"], w_scale=layer.wo_scale, **self._rows_modes)
             # (one sequence on the ShadowKV cache with near_fetch: the launch's first workgroups stage this step's near misses)
             near = None
             if attn_output.shape[0] == 1 and self.attn_mode != "full" and getattr(layer, "layer_idx", None) is not None:
@@ -383,15 +384,13 @@ class DecoderLM:
             residual, act = tensor_op.norm_linear_decode(o, residual, layer.post_attention_layernorm_weight,
                                                          layer.post_attention_layernorm_variance_epsilon,
                                                          layer.gate_up_proj, fuse_silu_mul=True, out=cur["act"], h_out=cur["h"],
-                                                         near_pull=near, w_scale=layer.gate_up_proj_scale, fp8_rows=self.fp8_rows,
-                                                         mxfp4_rows=self.mxfp4_rows)
+                                                         near_pull=near, w_scale=layer.gate_up_proj_scale, **self._rows_modes)
             if residual.shape[0] == 1:      # one sequence: the residual rides in the GEMV's bias slot (bf16(W.act) + residual,
                 #                             rounded like the separate add: same bits, one launch less)
                 near1 = None if near is None else self.kv_cache.near_pull_args(layer.layer_idx, 1)
                 return tensor_op.linear_decode(act, layer.down_proj, bias=residual, out=cur["out"], near_pull=near1,
-                                               w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows, mxfp4_rows=self.mxfp4_rows)
-            down = tensor_op.linear_decode(act, layer.down_proj, out=cur["down"], w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows,
-                                           mxfp4_rows=self.mxfp4_rows)
+                                               w_scale=layer.down_proj_scale, **self._rows_modes)
+            down = tensor_op.linear_decode(act, layer.down_proj, out=cur["down"], w_scale=layer.down_proj_scale, **self._rows_modes)
             return torch.add(residual, down, out=cur["out"])
         # (prefill: an FP8 layer's matrices are dequantised to bf16 temporaries as they are reached, each freed after its GEMM)
         hs = residual + F.linear(attn_output, layer.prefill_weight("wo"))
@@ -610,7 +609,7 @@ class DecoderLM:
                     x, residual, layer.input_layernorm_weight, layer.input_layernorm_variance_epsilon, layer.wqkv,
                     layer.bqkv, self.cos_sin_cache, pos, row_idx, kbuf, vbuf, self.num_heads,
                     self.num_key_value_heads, q_override=None if q_table is None else q_table[l], w_scale=layer.wqkv_scale,
-                    fp8_rows=self.fp8_rows, mxfp4_rows=self.mxfp4_rows)
+                    **self._rows_modes)
                 self.kv_proj_fused_launches += 1
             if overlap:
                 attn = c.select_fetch_attend_inplace(l, q, self.cos_sin_cache, kv_len=kv_len, kv_len_dev=kv_len_dev,
@@ -628,18 +627,16 @@ class DecoderLM:
                         c.fetch_kv_follows = False
                     c.fetch_kv(l, ids, self.cos_sin_cache)
                 attn = tensor_op.sparse_attention_decode(q, kbuf, vbuf, kv_len=kv_len, kv_len_dev=kv_len_dev, **slot_args)
-            o = tensor_op.linear_decode(attn.reshape(bs, 1, self.hidden_size), layer.wo, w_scale=layer.wo_scale, fp8_rows=self.fp8_rows,
-                                        mxfp4_rows=self.mxfp4_rows)
+            o = tensor_op.linear_decode(attn.reshape(bs, 1, self.hidden_size), layer.wo, w_scale=layer.wo_scale, **self._rows_modes)
             # residual add + RMSNorm ride in the gate/up GEMV's block-cooperative prologue (one launch when bs == 1
             # and hidden == 4096, bit-identical to add_rmsnorm + GEMV; otherwise norm_linear_decode splits it)
             residual, act = tensor_op.norm_linear_decode(o, residual, layer.post_attention_layernorm_weight,
                                                          layer.post_attention_layernorm_variance_epsilon,
                                                          layer.gate_up_proj, fuse_silu_mul=True,
                                                          near_pull=None if full or bs != 1 else c.near_pull_args(l),
-                                                         w_scale=layer.gate_up_proj_scale, fp8_rows=self.fp8_rows,
-                                                         mxfp4_rows=self.mxfp4_rows)
+                                                         w_scale=layer.gate_up_proj_scale, **self._rows_modes)
             x = tensor_op.linear_decode(act, layer.down_proj, near_pull=None if full or bs != 1 else c.near_pull_args(l, 1),
-                                        w_scale=layer.down_proj_scale, fp8_rows=self.fp8_rows, mxfp4_rows=self.mxfp4_rows)
+                                        w_scale=layer.down_proj_scale, **self._rows_modes)
         V = self.lm_head.shape[0]
         rm = None
         if self.sampler_ranges and not as_float and x.is_cuda and tensor_op.range_max_supported(x.numel(), x.shape[-1], V):
@@ -648,8 +645,7 @@ class DecoderLM:
             rm = self._range_max
         self._last_range_max = rm
         _, logits = tensor_op.norm_linear_decode(x, residual, self.norm_weight, self.norm_variance_epsilon, self.lm_head,
-                                                 range_max=rm, w_scale=self.lm_head_scale, fp8_rows=self.fp8_rows,
-                                                 mxfp4_rows=self.mxfp4_rows)
+                                                 range_max=rm, w_scale=self.lm_head_scale, **self._rows_modes)
         return logits.float() if as_float else logits        # (the native sampler reads the bf16 row as it is)
 
     def get_ctx(self, input_ids):
@@ -664,7 +660,7 @@ class DecoderLM:
             hs = self.layer_compute(self.layers[idx], idx, hs, position_ids)
         if hs.shape[1] == 1 and hs.is_cuda:
             _, logits = tensor_op.norm_linear_decode(hs, None, self.norm_weight, self.norm_variance_epsilon, self.lm_head,
-                                                     w_scale=self.lm_head_scale, fp8_rows=self.fp8_rows, mxfp4_rows=self.mxfp4_rows)
+                                                     w_scale=self.lm_head_scale, **self._rows_modes)
             return logits.float() if as_float else logits    # (bf16: tensor_op.sample_token then samples in one launch)
         hs = tensor_op.layer_norm(hs, self.norm_variance_epsilon, self.norm_weight)
         return F.linear(hs, self._lm_head_prefill()).float()

@@ -169,213 +169,143 @@ def _mxfp4_check_x(x, w, w_scale):
                          f"and scales uint8 [N, K / 32]")
 
 
-def _mxfp4_native(x, w, w_scale, rows):
-    """Shapes the MXFP4 GEMV kernels take: one token row, K % 32 == 0, K >= 1024, contiguous operands."""
-    K = x.shape[-1]
-    return rows == 1 and K % MXFP4_BLOCK == 0 and K >= MXFP4_MIN_K and x.is_contiguous() and w.is_contiguous() and w_scale.is_contiguous()
-
-
-def _mxfp4_native_rows(x, w, w_scale, rows):
-    """Shapes skv_linear_rows_mxfp4 takes: 2..MAX_GEMV_ROWS token rows on the GPU, K % 128 == 0, contiguous operands."""
-    return 2 <= rows <= MAX_GEMV_ROWS and x.shape[-1] % 128 == 0 and x.is_cuda and x.is_contiguous() and w.is_contiguous() \
-        and w_scale.is_contiguous()
-
-
-MXFP4_ROWS_MODES = ("fallback", "native")    # what 2..MAX_GEMV_ROWS token rows against an MXFP4 pair take (linear_decode)
-
-
-def _mxfp4_rows_check(mxfp4_rows):
-    if mxfp4_rows not in MXFP4_ROWS_MODES:
-        raise ValueError(f"mxfp4_rows must be one of {MXFP4_ROWS_MODES}, got {mxfp4_rows!r}")
-
-
-mxfp4_native_calls = 0    # native MXFP4 launches / dequantising fallbacks taken so far (diagnostics; the tests read them)
-mxfp4_fallback_calls = 0
-
-
-def _mxfp4_linear_fallback(x, w, w_scale, bias, fuse_silu_mul):
-    """CORRECT AND SLOW: the weights are dequantised to a bf16 temporary on every call, then F.linear (more than one token row
-    unless mxfp4_rows="native" serves them, K < 1024 at one row, non-contiguous operands)."""
-    global mxfp4_fallback_calls
-    mxfp4_fallback_calls += 1
-    out = F.linear(x, dequantize_mxfp4_rows(w, w_scale, x.dtype), bias)
-    return silu_and_mul_fused(out) if fuse_silu_mul else out
-
-
-def _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, mxfp4_rows="fallback"):
-    global mxfp4_native_calls
-    _mxfp4_check_x(x, w, w_scale)
-    N = w.shape[0]
-    native = _mxfp4_native(x, w, w_scale, rows)
-    if near_pull is not None:
-        if not native or fuse_silu_mul or N > 8192:
-            raise ValueError("near_pull rides in a one-token GEMV launch with at most 8,192 output rows")
-        y = out if out is not None else torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
-        check(lib().skv_gemv_near_pull_mxfp4(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, *near_pull,
-                                             current_stream_handle()), "gemv_near_pull_mxfp4")
-        mxfp4_native_calls += 1
-        return y
-    if mxfp4_rows == "native" and _mxfp4_native_rows(x, w, w_scale, rows):
-        y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
-        check(lib().skv_linear_rows_mxfp4(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), rows, N, K, 1 if fuse_silu_mul else 0,
-                                          current_stream_handle()), "linear_rows_mxfp4")
-        mxfp4_native_calls += 1
-        return y
-    if not native:
-        y = _mxfp4_linear_fallback(x, w, w_scale, bias, fuse_silu_mul)
-        return y if out is None else out.copy_(y)
-    y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
-    check(lib().skv_gemv_mxfp4(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0,
-                               current_stream_handle()), "gemv_mxfp4")
-    mxfp4_native_calls += 1
-    return y
-
-
-def _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
-                              mxfp4_rows="fallback"):
-    global mxfp4_native_calls
-    _mxfp4_check_x(x, w, w_scale)
-    K, N = x.shape[-1], w.shape[0]
-    one_launch = x.numel() == K == 4096 and x.is_contiguous() and w.is_contiguous() and w_scale.is_contiguous()
-    if near_pull is not None and (not one_launch or not fuse_silu_mul or bias is not None or range_max is not None):
-        raise ValueError("near_pull rides in the one-token gate/up launch (hidden size 4096, fused SiLU * mul, no bias)")
-    if range_max is not None and (not one_launch or fuse_silu_mul or not range_max_supported(x.numel(), K, N)):
-        raise ValueError("range_max: one token, hidden size 4096, N % 16 == 0, N <= 262,144, no fused SiLU")
-    if not one_launch:
-        h, hs = add_rmsnorm(x, residual, norm_w, eps)
-        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale, mxfp4_rows=mxfp4_rows)
-    y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
-    h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
-    head = (ptr(w), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0)
-    if near_pull is not None:
-        check(lib().skv_norm_gemv_near_pull_mxfp4(*head, ptr(y), N, K, *near_pull, current_stream_handle()),
-              "norm_gemv_near_pull_mxfp4")
-    elif range_max is not None:
-        check(lib().skv_norm_gemv_rangemax_mxfp4(*head, ptr(bias), ptr(y), N, K, ptr(range_max), current_stream_handle()),
-              "norm_gemv_rangemax_mxfp4")
-    else:
-        check(lib().skv_norm_gemv_mxfp4(*head, ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0, current_stream_handle()),
-              "norm_gemv_mxfp4")
-    mxfp4_native_calls += 1
-    return h, y
-
-
-def _fp8_check(w, w_scale):
+def _fp8_check_x(x, w, w_scale):
     if w.dtype != torch.float8_e4m3fn:
         raise ValueError("w_scale goes with float8_e4m3fn weights")
     if w_scale.dtype != torch.float32 or w_scale.numel() != w.shape[0] or not w_scale.is_contiguous():
         raise ValueError("w_scale must be a contiguous f32 vector with one entry per weight row")
 
 
-def _fp8_native(x, w, rows):
-    """Shapes the FP8 GEMV kernels take: one token row, K % 16 == 0, K >= 1024, contiguous operands."""
-    K = x.shape[-1]
-    return rows == 1 and K % 16 == 0 and K >= 1024 and x.is_contiguous() and w.is_contiguous()
-
-
-def _fp8_native_rows(x, w, rows):
-    """Shapes skv_linear_rows_fp8 takes: 2..MAX_GEMV_ROWS token rows, K % 64 == 0, contiguous operands."""
-    return 2 <= rows <= MAX_GEMV_ROWS and x.shape[-1] % 64 == 0 and x.is_contiguous() and w.is_contiguous()
-
-
-FP8_ROWS_MODES = ("fallback", "native")    # what 2..MAX_GEMV_ROWS token rows against FP8 weights take (linear_decode)
-
-
-def _fp8_rows_check(fp8_rows):
-    if fp8_rows not in FP8_ROWS_MODES:
-        raise ValueError(f"fp8_rows must be one of {FP8_ROWS_MODES}, got {fp8_rows!r}")
-
+# ---------------------------------------------------------------------------- decode projections: one dispatch, three weight formats
+MAX_GEMV_ROWS = 32   # token rows served by the native kernels (1: GEMV, 2..32: small-M MFMA kernel); more -> F.linear
+FP8_ROWS_MODES = ("fallback", "native")      # what 2..MAX_GEMV_ROWS token rows against FP8 weights take (linear_decode)
+MXFP4_ROWS_MODES = ("fallback", "native")    # what 2..MAX_GEMV_ROWS token rows against an MXFP4 pair take (linear_decode)
 
 fp8_native_calls = 0      # native FP8 launches / dequantising fallbacks taken so far (diagnostics; the tests read them)
 fp8_fallback_calls = 0
+mxfp4_native_calls = 0    # the same for MXFP4
+mxfp4_fallback_calls = 0
 
 
-def _fp8_linear_fallback(x, w, w_scale, bias, fuse_silu_mul):
-    """CORRECT AND SLOW: the weights are dequantised to a bf16 temporary on every call, then F.linear (more than one token row
-    unless fp8_rows="native" serves them, K < 1024 at one row, non-contiguous operands)."""
-    global fp8_fallback_calls
-    fp8_fallback_calls += 1
-    out = F.linear(x, dequantize_fp8_rows(w, w_scale, x.dtype), bias)
-    return silu_and_mul_fused(out) if fuse_silu_mul else out
+class _WeightFormat:
+    """What differs between the weight formats of the decode projections; everything else is the one path of linear_decode,
+    norm_linear_decode and norm_qkv_rope_update.  Three records, built once below; a call only reads one.
+      weight_dtype              the name DecoderLM knows the format by
+      gemv, gemv_near_pull, norm_gemv, norm_gemv_rangemax, norm_gemv_near_pull, linear_rows, qkv_gemv_rope_update
+                                the symbol of the format's native entry of each kind ("skv_" + kind + suffix)
+      validate(x, w, w_scale)   raises ValueError for a (w, w_scale) pair the format does not take; None: nothing to check
+      scaled                    w_scale follows w in every native call; the scaled formats are the counted ones
+      k_step, k_min             one token row is native with K % k_step == 0 and K >= k_min and contiguous x and w -
+      scale_contiguous          - and, where set, a contiguous w_scale
+      rows_k_step, rows_k_min   2..MAX_GEMV_ROWS token rows are native with K % rows_k_step == 0, K >= rows_k_min, the same
+      rows_keyword, rows_gpu    contiguity, the keyword of this name (None: always) set to "native", and, where rows_gpu, x.is_cuda
+      quantize(w, pow2_scale), dequantize(w, w_scale, dtype)    bf16 <-> the format (None: bf16 itself)
+      native_counter, fallback_counter                          names of the module's call counters (None: bf16, not counted)"""
+    KINDS = ("gemv", "gemv_near_pull", "norm_gemv", "norm_gemv_rangemax", "norm_gemv_near_pull", "linear_rows", "qkv_gemv_rope_update")
+    __slots__ = KINDS + ("weight_dtype", "what", "validate", "scaled", "k_step", "k_min", "scale_contiguous", "rows_k_step", "rows_k_min",
+                         "rows_keyword", "rows_gpu", "quantize", "dequantize", "native_counter", "fallback_counter")
+
+    def __init__(self, weight_dtype, suffix, what_suffix, qkv_suffix, **fields):
+        self.weight_dtype = weight_dtype
+        self.what = {}                  # symbol -> the name a native error carries (bf16: the kind alone)
+        for kind in self.KINDS:
+            qkv = kind == "qkv_gemv_rope_update"
+            setattr(self, kind, "skv_" + kind + (qkv_suffix if qkv else suffix))
+            self.what[getattr(self, kind)] = kind + (qkv_suffix if qkv else what_suffix)
+        for name, value in fields.items():
+            setattr(self, name, value)
 
 
-MAX_GEMV_ROWS = 32   # token rows served by the native kernels (1: GEMV, 2..32: small-M MFMA kernel); more -> F.linear
+_BF16 = _WeightFormat("bf16", "_bf16", "", "", validate=None, scaled=False, k_step=32, k_min=512, scale_contiguous=False,
+                      rows_k_step=32, rows_k_min=512, rows_keyword=None, rows_gpu=False, quantize=None, dequantize=None,
+                      native_counter=None, fallback_counter=None)
+_FP8 = _WeightFormat("fp8_e4m3", "_fp8", "_fp8", "_fp8", validate=_fp8_check_x, scaled=True, k_step=16, k_min=1024, scale_contiguous=False,
+                     rows_k_step=64, rows_k_min=0, rows_keyword="fp8_rows", rows_gpu=False,
+                     quantize=quantize_fp8_rows, dequantize=dequantize_fp8_rows,
+                     native_counter="fp8_native_calls", fallback_counter="fp8_fallback_calls")
+_MXFP4 = _WeightFormat("mxfp4", "_mxfp4", "_mxfp4", "_mxfp4", validate=_mxfp4_check_x, scaled=True, k_step=MXFP4_BLOCK, k_min=MXFP4_MIN_K,
+                       scale_contiguous=True, rows_k_step=128, rows_k_min=0, rows_keyword="mxfp4_rows", rows_gpu=True,
+                       quantize=lambda w, pow2_scale=False: quantize_mxfp4_rows(w), dequantize=dequantize_mxfp4_rows,
+                       native_counter="mxfp4_native_calls", fallback_counter="mxfp4_fallback_calls")
+WEIGHT_FORMATS = {f.weight_dtype: f for f in (_BF16, _FP8, _MXFP4)}
+
+
+def weight_format(w, w_scale):
+    """The record of a (w, w_scale) pair: uint8 weights are MXFP4 nibbles, any other weights with a scale are FP8, weights without
+    one are bf16 (as it has been: a bf16 matrix WITH a scale is refused by the FP8 check, FP8 bytes WITHOUT one are not caught)."""
+    if w.dtype == torch.uint8:
+        return _MXFP4
+    return _FP8 if w_scale is not None else _BF16
+
+
+def _rows_modes_refuse(fp8_rows, mxfp4_rows):
+    if fp8_rows not in FP8_ROWS_MODES:
+        raise ValueError(f"fp8_rows must be one of {FP8_ROWS_MODES}, got {fp8_rows!r}")
+    raise ValueError(f"mxfp4_rows must be one of {MXFP4_ROWS_MODES}, got {mxfp4_rows!r}")
+
+
+def _linear_fallback(fmt, x, w, w_scale, bias, fuse_silu_mul, out):
+    """F.linear.  A quantised format is CORRECT AND SLOW here: the weights are dequantised to a temporary of x's dtype on every
+    call (counted).  What becomes of `out` differs and is carried as it has been: the quantised formats copy the result into it
+    and return it, bf16 returns F.linear's own tensor and leaves `out` untouched."""
+    if fmt.dequantize is None:
+        y = F.linear(x, w, bias)
+        return silu_and_mul_fused(y) if fuse_silu_mul else y
+    globals()[fmt.fallback_counter] += 1
+    y = F.linear(x, fmt.dequantize(w, w_scale, x.dtype), bias)
+    if fuse_silu_mul:
+        y = silu_and_mul_fused(y)
+    return y if out is None else out.copy_(y)
 
 
 def linear_decode(x, w, bias=None, fuse_silu_mul=False, out=None, near_pull=None, w_scale=None, fp8_rows="fallback",
                   mxfp4_rows="fallback"):
-    """F.linear for decode-time activations (x [..., K] with a handful of token rows): one token -> the native GEMV,
-    2..MAX_GEMV_ROWS tokens -> the native small-M MFMA kernel (weights stream once); falls back to F.linear for more
-    rows or shapes the kernels are not built for.  fuse_silu_mul: w = [gate; up] -> silu(gate.x) * (up.x).
-    near_pull (the down projection of a ShadowKV layer, one token, N <= 8192; ShadowKVCache_CPU.near_pull_args(layer, 1)): the
-    launch's first workgroups stage the second near-miss list of this step's selection (skv_gemv_near_pull_bf16); same y.
-    w_scale (f32 [N]): w holds float8_e4m3fn bytes (quantize_fp8_rows) - one token takes the native FP8 GEMV; more token rows,
-    K < 1024 or non-contiguous operands fall back to F.linear over the dequantised weights (correct, slow).
-    fp8_rows ("fallback" | "native"; read with w_scale only): "native" sends 2..MAX_GEMV_ROWS contiguous token rows with
-    K % 64 == 0 through skv_linear_rows_fp8 - the FP8 bytes stream once, nothing is dequantised; every
-    other multi-row shape still falls back.  One token row, near_pull and the default are unchanged.
-    w uint8 [N, K / 2] with w_scale uint8 [N, K / 32] (quantize_mxfp4_rows): an MXFP4 pair - one contiguous token row with
-    K % 32 == 0 and K >= 1024 takes the native MXFP4 GEMV (near_pull included), everything else the dequantising fallback;
-    fp8_rows is not read.
-    mxfp4_rows ("fallback" | "native"; read with an MXFP4 pair only): "native" sends 2..MAX_GEMV_ROWS contiguous token rows on
-    the GPU with K % 128 == 0 through skv_linear_rows_mxfp4 - the nibbles stream once, nothing is dequantised (DESIGN.md section
-    12.1); every other multi-row shape still falls back.  One token row, near_pull and the default are unchanged."""
-    _fp8_rows_check(fp8_rows)
-    _mxfp4_rows_check(mxfp4_rows)
+    """F.linear for decode-time activations (x [..., K] with a handful of token rows).  fuse_silu_mul: w = [gate; up] ->
+    silu(gate.x) * (up.x).  out: a caller-owned result buffer.  The weight format follows from (w, w_scale) - weight_format();
+    for every format, in this order:
+      near_pull (the down projection of a ShadowKV layer; ShadowKVCache_CPU.near_pull_args(layer, 1)): one native token row with
+        N <= 8192 and no fused SiLU, else ValueError; the GEMV launch's first workgroups stage the second near-miss list of this
+        step's selection (skv_gemv_near_pull_<format>); same y.
+      2..MAX_GEMV_ROWS native token rows -> the small-M MFMA kernel (skv_linear_rows_<format>): the weights stream once.
+      anything else but one native token row -> F.linear, over dequantised weights where the format is quantised (correct, slow).
+      one native token row -> the GEMV (skv_gemv_<format>).
+    Native means contiguous x and w and a K the format's kernels take:
+      format  w, w_scale                                          one row            2..32 rows                        counted
+      bf16    bf16 [N, K], None                                   K % 32, K >= 512   the same                          no
+      FP8     float8_e4m3fn [N, K], f32 [N] (quantize_fp8_rows)   K % 16, K >= 1024  fp8_rows="native", K % 64         fp8_*_calls
+      MXFP4   uint8 [N, K / 2], uint8 [N, K / 32], contiguous     K % 32, K >= 1024  mxfp4_rows="native", K % 128,     mxfp4_*_calls
+              (quantize_mxfp4_rows)                                                  x on the GPU
+    fp8_rows / mxfp4_rows ("fallback" | "native") are checked on every call and read by their own format only (DESIGN.md
+    sections 10, 10.1, 12, 12.1)."""
+    if fp8_rows not in FP8_ROWS_MODES or mxfp4_rows not in MXFP4_ROWS_MODES:
+        _rows_modes_refuse(fp8_rows, mxfp4_rows)
     K = x.shape[-1]
     rows = x.numel() // K
-    if w.dtype == torch.uint8:          # an MXFP4 pair (fp8_rows does not apply to it)
-        return _linear_decode_mxfp4(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, mxfp4_rows)
-    if w_scale is not None:
-        return _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, fp8_rows)
-    if near_pull is not None:
-        N = w.shape[0]
-        if rows != 1 or fuse_silu_mul or N > 8192 or K % 32 or K < 512 or not x.is_contiguous() or not w.is_contiguous():
-            raise ValueError("near_pull rides in a one-token GEMV launch with at most 8,192 output rows")
-        y = out if out is not None else torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
-        check(lib().skv_gemv_near_pull_bf16(ptr(w), ptr(x), ptr(bias), ptr(y), N, K, *near_pull, current_stream_handle()),
-              "gemv_near_pull")
-        return y
-    if rows > MAX_GEMV_ROWS or K % 32 or K < 512 or not x.is_contiguous() or not w.is_contiguous():
-        out = F.linear(x, w, bias)
-        return silu_and_mul_fused(out) if fuse_silu_mul else out
+    fmt = _MXFP4 if w.dtype == torch.uint8 else _FP8 if w_scale is not None else _BF16         # weight_format(w, w_scale)
+    if fmt.validate is not None:
+        fmt.validate(x, w, w_scale)
     N = w.shape[0]
-    No = (N // 2) if fuse_silu_mul else N
-    y = out if out is not None else torch.empty(x.shape[:-1] + (No,), dtype=x.dtype, device=x.device)
-    if rows == 1:
-        check(lib().skv_gemv_bf16(ptr(w), ptr(x), ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0,
-                                  current_stream_handle()), "gemv")
+    contiguous = x.is_contiguous() and w.is_contiguous() and (not fmt.scale_contiguous or w_scale.is_contiguous())
+    one_row = rows == 1 and contiguous and K % fmt.k_step == 0 and K >= fmt.k_min
+    if near_pull is not None:
+        if not one_row or fuse_silu_mul or N > 8192:
+            raise ValueError("near_pull rides in a one-token GEMV launch with at most 8,192 output rows")
+        symbol, tail = fmt.gemv_near_pull, (N, K) + tuple(near_pull)
+    elif 2 <= rows <= MAX_GEMV_ROWS and contiguous and K % fmt.rows_k_step == 0 and K >= fmt.rows_k_min \
+            and (fmt.rows_keyword is None or (fp8_rows if fmt.rows_keyword == "fp8_rows" else mxfp4_rows) == "native") \
+            and (x.is_cuda or not fmt.rows_gpu):
+        symbol, tail = fmt.linear_rows, (rows, N, K, 1 if fuse_silu_mul else 0)
+    elif not one_row:
+        return _linear_fallback(fmt, x, w, w_scale, bias, fuse_silu_mul, out)
     else:
-        check(lib().skv_linear_rows_bf16(ptr(w), ptr(x), ptr(bias), ptr(y), rows, N, K, 1 if fuse_silu_mul else 0,
-                                         current_stream_handle()), "linear_rows")
-    return y
-
-
-def _linear_decode_fp8(x, w, w_scale, bias, fuse_silu_mul, out, near_pull, K, rows, fp8_rows="fallback"):
-    global fp8_native_calls
-    _fp8_check(w, w_scale)
-    N = w.shape[0]
-    if near_pull is not None:
-        if not _fp8_native(x, w, rows) or fuse_silu_mul or N > 8192:
-            raise ValueError("near_pull rides in a one-token GEMV launch with at most 8,192 output rows")
-        y = out if out is not None else torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
-        check(lib().skv_gemv_near_pull_fp8(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, *near_pull,
-                                           current_stream_handle()), "gemv_near_pull_fp8")
-        fp8_native_calls += 1
-        return y
-    if fp8_rows == "native" and _fp8_native_rows(x, w, rows):
-        y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
-        check(lib().skv_linear_rows_fp8(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), rows, N, K, 1 if fuse_silu_mul else 0,
-                                        current_stream_handle()), "linear_rows_fp8")
-        fp8_native_calls += 1
-        return y
-    if not _fp8_native(x, w, rows):
-        y = _fp8_linear_fallback(x, w, w_scale, bias, fuse_silu_mul)
-        return y if out is None else out.copy_(y)
+        symbol, tail = fmt.gemv, (N, K, 1 if fuse_silu_mul else 0)
     y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
-    check(lib().skv_gemv_fp8(ptr(w), ptr(w_scale), ptr(x), ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0,
-                             current_stream_handle()), "gemv_fp8")
-    fp8_native_calls += 1
+    head = (ptr(w), ptr(w_scale)) if fmt.scaled else (ptr(w),)
+    rc = getattr(lib(), symbol)(*head, ptr(x), ptr(bias), ptr(y), *tail, current_stream_handle())
+    if rc:
+        check(rc, fmt.what[symbol])
+    if fmt.scaled:
+        globals()[fmt.native_counter] += 1
     return y
 
 
@@ -386,82 +316,47 @@ def range_max_supported(x_numel, K, N):
 
 def norm_linear_decode(x, residual, norm_w, eps, w, bias=None, fuse_silu_mul=False, out=None, h_out=None, range_max=None,
                        near_pull=None, w_scale=None, fp8_rows="fallback", mxfp4_rows="fallback"):
-    """(h, y): h = x + residual (residual None -> h = x), y = linear(RMSNorm(h) * norm_w) for one token, one
-    native launch when the hidden size is 4096; otherwise add_rmsnorm + linear_decode.  out / h_out: caller-owned
-    result buffers (the eager decode paths reuse theirs instead of allocating per call).
-    range_max (lm_head only; int16 [>= N // 16], 16-B aligned; range_max_supported(...) must hold): the launch also leaves the
-    largest of every 16 outputs as the sampler's 16-bit key (sample_token_native(..., range_max=)).
-    near_pull (gate/up launch of a ShadowKV layer only; ShadowKVCache_CPU.near_pull_args(layer)): the launch's first workgroups
-    stage the near misses of this step's selection ahead of the next step (skv_norm_gemv_near_pull_bf16); same y.
-    w_scale (f32 [N]): w holds float8_e4m3fn bytes - the same one-launch paths with the FP8 kernels (same h, bit for bit);
-    other shapes: add_rmsnorm + linear_decode(..., w_scale=, fp8_rows=) - fp8_rows as in linear_decode.
-    An MXFP4 pair (w uint8 [N, K / 2], w_scale uint8 [N, K / 32]) takes the same paths with the MXFP4 kernels; other shapes:
-    add_rmsnorm + linear_decode(..., w_scale=, mxfp4_rows=) - mxfp4_rows as in linear_decode."""
-    _fp8_rows_check(fp8_rows)
-    _mxfp4_rows_check(mxfp4_rows)
+    """(h, y): h = x + residual (residual None -> h = x), y = linear(RMSNorm(h) * norm_w).  One token with hidden size 4096 and
+    contiguous operands (x, w; MXFP4: and w_scale) is one native launch, skv_norm_gemv_<format> (the same h, bit for bit, in every
+    format); anything else is add_rmsnorm + linear_decode(..., w_scale=, fp8_rows=, mxfp4_rows=) - formats and keywords as in
+    linear_decode.  out / h_out: caller-owned result buffers (the eager decode paths reuse theirs instead of allocating per call).
+    Two roles ride in the one launch only - ValueError elsewhere:
+      near_pull (gate/up launch of a ShadowKV layer: fused SiLU, no bias, no range_max; ShadowKVCache_CPU.near_pull_args(layer)):
+        the launch's first workgroups stage the near misses of this step's selection ahead of the next step
+        (skv_norm_gemv_near_pull_<format>); same y.
+      range_max (lm_head: no fused SiLU; int16 [>= N // 16], 16-B aligned; range_max_supported(...) must hold): the launch also
+        leaves the largest of every 16 outputs as the sampler's 16-bit key (sample_token_native(..., range_max=))."""
+    if fp8_rows not in FP8_ROWS_MODES or mxfp4_rows not in MXFP4_ROWS_MODES:
+        _rows_modes_refuse(fp8_rows, mxfp4_rows)
     K = x.shape[-1]
+    fmt = _MXFP4 if w.dtype == torch.uint8 else _FP8 if w_scale is not None else _BF16         # weight_format(w, w_scale)
+    if fmt.validate is not None:
+        fmt.validate(x, w, w_scale)
     N = w.shape[0]
-    if w.dtype == torch.uint8:          # an MXFP4 pair (fp8_rows does not apply to it)
-        return _norm_linear_decode_mxfp4(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
-                                         mxfp4_rows)
-    if w_scale is not None:
-        return _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
-                                       fp8_rows)
-    if near_pull is not None:
-        if not fuse_silu_mul or bias is not None or range_max is not None or x.numel() != K or K != 4096 \
-                or not x.is_contiguous() or not w.is_contiguous():
-            raise ValueError("near_pull rides in the one-token gate/up launch (hidden size 4096, fused SiLU * mul, no bias)")
-        y = out if out is not None else torch.empty(x.shape[:-1] + (N // 2,), dtype=x.dtype, device=x.device)
-        h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
-        check(lib().skv_norm_gemv_near_pull_bf16(ptr(w), ptr(x), ptr(residual), ptr(norm_w), float(eps),
-                                                 ptr(h) if residual is not None else 0, ptr(y), N, K, *near_pull,
-                                                 current_stream_handle()), "norm_gemv_near_pull")
-        return h, y
-    if range_max is not None:
-        if fuse_silu_mul or not range_max_supported(x.numel(), K, N) or not x.is_contiguous() or not w.is_contiguous():
-            raise ValueError("range_max: one token, hidden size 4096, N % 16 == 0, N <= 262,144, no fused SiLU")
-        y = out if out is not None else torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
-        h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
-        check(lib().skv_norm_gemv_rangemax_bf16(ptr(w), ptr(x), ptr(residual), ptr(norm_w), float(eps),
-                                                ptr(h) if residual is not None else 0, ptr(bias), ptr(y), N, K, ptr(range_max),
-                                                current_stream_handle()), "norm_gemv_rangemax")
-        return h, y
-    if x.numel() != K or K != 4096 or not x.is_contiguous() or not w.is_contiguous():
-        h, hs = add_rmsnorm(x, residual, norm_w, eps)
-        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out)
-    y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
-    h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
-    check(lib().skv_norm_gemv_bf16(ptr(w), ptr(x), ptr(residual), ptr(norm_w), float(eps),
-                                   ptr(h) if residual is not None else 0, ptr(bias), ptr(y), N, K,
-                                   1 if fuse_silu_mul else 0, current_stream_handle()), "norm_gemv")
-    return h, y
-
-
-def _norm_linear_decode_fp8(x, residual, norm_w, eps, w, w_scale, bias, fuse_silu_mul, out, h_out, range_max, near_pull,
-                            fp8_rows="fallback"):
-    global fp8_native_calls
-    _fp8_check(w, w_scale)
-    K, N = x.shape[-1], w.shape[0]
-    one_launch = x.numel() == K == 4096 and x.is_contiguous() and w.is_contiguous()
+    one_launch = x.numel() == K == 4096 and x.is_contiguous() and w.is_contiguous() \
+        and (not fmt.scale_contiguous or w_scale.is_contiguous())
     if near_pull is not None and (not one_launch or not fuse_silu_mul or bias is not None or range_max is not None):
         raise ValueError("near_pull rides in the one-token gate/up launch (hidden size 4096, fused SiLU * mul, no bias)")
     if range_max is not None and (not one_launch or fuse_silu_mul or not range_max_supported(x.numel(), K, N)):
         raise ValueError("range_max: one token, hidden size 4096, N % 16 == 0, N <= 262,144, no fused SiLU")
     if not one_launch:
         h, hs = add_rmsnorm(x, residual, norm_w, eps)
-        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale, fp8_rows=fp8_rows)
+        return h, linear_decode(hs, w, bias, fuse_silu_mul, out=out, w_scale=w_scale, fp8_rows=fp8_rows, mxfp4_rows=mxfp4_rows)
     y = out if out is not None else torch.empty(x.shape[:-1] + ((N // 2) if fuse_silu_mul else N,), dtype=x.dtype, device=x.device)
     h = (h_out if h_out is not None else torch.empty_like(x)) if residual is not None else x
-    head = (ptr(w), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0)
     if near_pull is not None:
-        check(lib().skv_norm_gemv_near_pull_fp8(*head, ptr(y), N, K, *near_pull, current_stream_handle()), "norm_gemv_near_pull_fp8")
+        symbol, tail = fmt.norm_gemv_near_pull, (ptr(y), N, K) + tuple(near_pull)
     elif range_max is not None:
-        check(lib().skv_norm_gemv_rangemax_fp8(*head, ptr(bias), ptr(y), N, K, ptr(range_max), current_stream_handle()),
-              "norm_gemv_rangemax_fp8")
+        symbol, tail = fmt.norm_gemv_rangemax, (ptr(bias), ptr(y), N, K, ptr(range_max))
     else:
-        check(lib().skv_norm_gemv_fp8(*head, ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0, current_stream_handle()),
-              "norm_gemv_fp8")
-    fp8_native_calls += 1
+        symbol, tail = fmt.norm_gemv, (ptr(bias), ptr(y), N, K, 1 if fuse_silu_mul else 0)
+    head = (ptr(w), ptr(w_scale)) if fmt.scaled else (ptr(w),)
+    rc = getattr(lib(), symbol)(*head, ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0, *tail,
+                                current_stream_handle())
+    if rc:
+        check(rc, fmt.what[symbol])
+    if fmt.scaled:
+        globals()[fmt.native_counter] += 1
     return h, y
 
 
@@ -504,51 +399,32 @@ def qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_he
 def norm_qkv_rope_update(x, residual, norm_w, eps, wqkv, bqkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads,
                          kv_heads, q_override=None, w_scale=None, fp8_rows="fallback", mxfp4_rows="fallback"):
     """(h, q) for ONE token of ONE sequence: h = x + residual, q = RoPE(split(linear(RMSNorm(h)))) [1, Hq, 1, D];
-    rotated k and v are pushed into row row_idx of k_cache / v_cache [1, Hkv, rows, D].  One native launch when the
-    hidden size is 4096 and bs == 1; otherwise norm_linear_decode + qkv_rope_update.
-    w_scale (f32 [rows of wqkv]): wqkv holds float8_e4m3fn bytes - the same two paths with the FP8 kernels; fp8_rows as in
-    linear_decode (the multi-row path's projection).  An MXFP4 pair (wqkv uint8 [N, K / 2], w_scale uint8 [N, K / 32]) takes
-    the same two paths with the MXFP4 kernels; mxfp4_rows as in linear_decode (the multi-row path's projection)."""
-    global fp8_native_calls, mxfp4_native_calls
-    _fp8_rows_check(fp8_rows)
-    _mxfp4_rows_check(mxfp4_rows)
+    rotated k and v are pushed into row row_idx of k_cache / v_cache [1, Hkv, rows, D].  One native launch
+    (skv_qkv_gemv_rope_update[_<format>]) when the hidden size is 4096, head_dim 128, bs == 1 and the operands are contiguous
+    (x, wqkv; MXFP4: and w_scale); otherwise norm_linear_decode + qkv_rope_update.  Formats (wqkv, w_scale) and the rows keywords
+    (the multi-row path's projection) as in linear_decode."""
+    if fp8_rows not in FP8_ROWS_MODES or mxfp4_rows not in MXFP4_ROWS_MODES:
+        _rows_modes_refuse(fp8_rows, mxfp4_rows)
     K = x.shape[-1]
     D = k_cache.shape[-1]
-    mx = wqkv.dtype == torch.uint8
-    if mx:
-        _mxfp4_check_x(x, wqkv, w_scale)
-    elif w_scale is not None:
-        _fp8_check(wqkv, w_scale)
+    fmt = _MXFP4 if wqkv.dtype == torch.uint8 else _FP8 if w_scale is not None else _BF16      # weight_format(wqkv, w_scale)
+    if fmt.validate is not None:
+        fmt.validate(x, wqkv, w_scale)
     if x.numel() != K or K != 4096 or not x.is_contiguous() or not wqkv.is_contiguous() or D != 128 \
-            or (mx and not w_scale.is_contiguous()):
+            or (fmt.scale_contiguous and not w_scale.is_contiguous()):
         h, qkv = norm_linear_decode(x, residual, norm_w, eps, wqkv, bqkv, w_scale=w_scale, fp8_rows=fp8_rows, mxfp4_rows=mxfp4_rows)
         return h, qkv_rope_update(qkv, cos_sin, pos, row_idx, k_cache, v_cache, q_heads, kv_heads, q_override)
     q = torch.empty(1, q_heads, 1, D, dtype=x.dtype, device=x.device)
     h = torch.empty_like(x) if residual is not None else x
-    if mx:
-        check(lib().skv_qkv_gemv_rope_update_mxfp4(ptr(wqkv), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps),
-                                                   ptr(h) if residual is not None else 0, ptr(bqkv), ptr(cos_sin), ptr(pos),
-                                                   ptr(row_idx), ptr(q_override), ptr(q), ptr(k_cache), ptr(v_cache), K, q_heads,
-                                                   kv_heads, D, cos_sin.stride(0), cos_sin.shape[0], k_cache.stride(1),
-                                                   k_cache.shape[2], 1 if cos_sin.shape[-1] == 128 else 2, current_stream_handle()),
-              "qkv_gemv_rope_update_mxfp4")
-        mxfp4_native_calls += 1
-        return h, q
-    if w_scale is not None:
-        check(lib().skv_qkv_gemv_rope_update_fp8(ptr(wqkv), ptr(w_scale), ptr(x), ptr(residual), ptr(norm_w), float(eps),
-                                                 ptr(h) if residual is not None else 0, ptr(bqkv), ptr(cos_sin), ptr(pos),
-                                                 ptr(row_idx), ptr(q_override), ptr(q), ptr(k_cache), ptr(v_cache), K, q_heads,
-                                                 kv_heads, D, cos_sin.stride(0), cos_sin.shape[0], k_cache.stride(1),
-                                                 k_cache.shape[2], 1 if cos_sin.shape[-1] == 128 else 2, current_stream_handle()),
-              "qkv_gemv_rope_update_fp8")
-        fp8_native_calls += 1
-        return h, q
-    check(lib().skv_qkv_gemv_rope_update(ptr(wqkv), ptr(x), ptr(residual), ptr(norm_w), float(eps),
-                                         ptr(h) if residual is not None else 0, ptr(bqkv), ptr(cos_sin), ptr(pos),
-                                         ptr(row_idx), ptr(q_override), ptr(q), ptr(k_cache), ptr(v_cache), K, q_heads,
-                                         kv_heads, D, cos_sin.stride(0), cos_sin.shape[0], k_cache.stride(1),
-                                         k_cache.shape[2], 1 if cos_sin.shape[-1] == 128 else 2, current_stream_handle()),
-          "qkv_gemv_rope_update")
+    head = (ptr(wqkv), ptr(w_scale)) if fmt.scaled else (ptr(wqkv),)
+    rc = getattr(lib(), fmt.qkv_gemv_rope_update)(
+        *head, ptr(x), ptr(residual), ptr(norm_w), float(eps), ptr(h) if residual is not None else 0, ptr(bqkv), ptr(cos_sin), ptr(pos),
+        ptr(row_idx), ptr(q_override), ptr(q), ptr(k_cache), ptr(v_cache), K, q_heads, kv_heads, D, cos_sin.stride(0), cos_sin.shape[0],
+        k_cache.stride(1), k_cache.shape[2], 1 if cos_sin.shape[-1] == 128 else 2, current_stream_handle())
+    if rc:
+        check(rc, fmt.what[fmt.qkv_gemv_rope_update])
+    if fmt.scaled:
+        globals()[fmt.native_counter] += 1
     return h, q
 
 
