@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import decode_model_ref as dmr
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 PROMPT = 4700          # > 4096 (the ShadowKV prefill branch), not a multiple of any tile or chunk
@@ -164,11 +166,38 @@ def test_full_mode_continuation(glm):
         _make(glm=glm).prefill_cont(ids[:, :10])
 
 
+def _tap_decode_steps(m, ids):
+    """Wraps m.forward_fused (the pattern of tests/test_gpu_fp8_model.py::_tap): the f64 state of the prefilled prompt is taken
+    at the first decode step - after generate()'s prefill and H2D, before anything steps - and every step leaves (its input
+    token, its logits, the chunk sets position_ids names afterwards).  -> (box with "state", the list of steps)"""
+    box, steps, orig = {}, [], m.forward_fused
+
+    def ff(token, *a, **k):
+        if "state" not in box:
+            box["state"] = dmr.snapshot_prefilled(m, ids)
+        tok = token.clone()
+        out = orig(token, *a, **k)
+        c = m.kv_cache
+        steps.append((tok, out[:, -1].float(), [c.position_ids[l][:, :, :c.select_sets].clone() for l in range(m.num_layers)]))
+        return out
+
+    m.forward_fused = ff
+    return box, steps
+
+
 @pytest.mark.parametrize("attn_mode", ["shadowkv_cpu", "full"])
 @pytest.mark.parametrize("glm", [False, True])
 def test_greedy_generate_follows_restatement(glm, attn_mode):
+    """ShadowKV branch, decode steps: the tokens leave the FULL-attention restatement (256 of 4,700 rows are attended), so each
+    step's logits are checked against the restatement of the sparse step itself (tests/decode_model_ref.py: the prompt's K / V
+    from an f64 dense forward, exact K for the chunks resident since the prefill and RoPE(U . SV) for the misses, the set the
+    cache selected, the tokens generate() produced) under LOGIT_BOUND.  Measured on one MI355X, max |d| / max |logit| over the 8
+    steps: see profiles/decode_model_ref.txt.  The norm weights are distinct random vectors (1 + 0.25 N(0, 1))."""
     m = _make(glm=glm, attn_mode=attn_mode)
+    dmr.randomize_norm_weights(m, 41)
     ids = _ids(1, PROMPT, seed=10)
+    if attn_mode != "full":
+        box, steps = _tap_decode_steps(m, ids)
     gen = m.generate(ids, 8, temperature=0.0)
     torch.cuda.synchronize()
     assert gen.shape == (1, 9) and gen.dtype == torch.long
@@ -185,6 +214,13 @@ def test_greedy_generate_follows_restatement(glm, attn_mode):
         # here), an approximation of the restatement's full attention that this random-weight model does not follow
         assert float(gap[0]) < LOGIT_BOUND
         assert bool(((gen >= 0) & (gen < 2000)).all())
+        assert len(steps) == 8 and [int(t) for t, _, _ in steps] == gen[0, :8].tolist()
+        st, dist = box["state"], []
+        for tok, logits, sets in steps:
+            dist.append(float(dmr.logit_distance(logits, dmr.step(st, tok, sets).logits).max()))
+        print(f"prefilled {'glm' if glm else 'neox'}: decode logits against the sparse restatement, max |d| / max |logit| per step = "
+              f"{[round(d, 5) for d in dist]}")
+        assert max(dist) < LOGIT_BOUND, dist
     assert m.kv_cache.get_kv_len() == PROMPT + 8
 
 
